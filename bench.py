@@ -13,6 +13,10 @@ Other BASELINE configs, for driver-visible numbers next to the headline:
                call; value = sampled video tokens / s.  Also reports the ART-V training step.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1 via `python -m torch.distributed.run ...`)
+  --dump-outputs DIR   rank 0 writes what the last timed step computed as DIR/<name>.npy (see dump_outputs()), so that two
+                       builds can be compared output for output.  For training, that last step starts from the freshly
+                       initialised weights and optimizer state (train_state(); the clock is paused while they are put back):
+                       its inputs then depend only on the arguments, not on the rounding of the steps before it
 
 Prints ONE JSON line on rank 0: value = whole-job video tokens / second, a `roofline` object for the dominant kernel
 (HIP events around every launch of one eagerly launched step right after the timed region) and, at N = 1 / config 2, a `cpu_baseline` object (the fp32 CPU oracle timed on
@@ -110,6 +114,82 @@ def eager_step(trainer, fn, batch):
     loss.backward()
     trainer.step()
     return loss.detach()
+
+
+DUMP_SAMPLE = 1 << 22  # elements of each flat trainer buffer written by --dump-outputs (16 MB in float32)
+DUMP_LIMIT = 64 << 20  # bytes, all files together
+
+
+def flat_sample_index(n, k=DUMP_SAMPLE, seed=0):
+    """A fixed, seeded sample of k positions of a flat buffer of n elements: one position drawn in each of k equal strides."""
+    if n <= k:
+        return np.arange(n)
+    stride = n / k
+    lo = np.floor(np.arange(k) * stride).astype(np.int64)
+    hi = np.floor(np.arange(1, k + 1) * stride).astype(np.int64)
+    return lo + (np.random.default_rng(seed).random(k) * (hi - lo)).astype(np.int64)
+
+
+def train_state(trainer):
+    """Everything a training step reads and updates: the flat fp32 weights, Adam moments and bf16 shadow, the device step / lr
+    counters, the lazy-row flags and the front end's device step (it seeds the masks and warps).  Taken right after the
+    trainer is built, it is a function of the arguments alone -- unlike the state after a few steps, which carries the
+    last-bit differences of the fp32 atomics in the backward (table scatter-add, bias and norm weight sums), amplified by Adam."""
+    z, fe = trainer._lazy, getattr(trainer.model, 'frontend', None)
+    return {'P': trainer.P.clone(), 'M': trainer.M.clone(), 'V': trainer.V.clone(), 'S': trainer.S.clone(),
+            'step_dev': trainer._step_dev.clone(), 'lr_dev': trainer._lr_dev.clone(), 'step_count': trainer.step_count,
+            'flags': None if z is None else z['flags'].clone(),
+            'fe_step': None if fe is None else (torch.zeros(1, device=trainer.P.device) if fe.step is None else fe.step.clone())}
+
+
+def restore_train_state(trainer, st):
+    """Put a train_state() back in place (same buffers, so a captured step graph replays on it); the gradient is cleared."""
+    for name in ('P', 'M', 'V', 'S'):
+        getattr(trainer, name).copy_(st[name])
+    trainer.G.zero_()
+    trainer._step_dev.copy_(st['step_dev'])
+    trainer._lr_dev.copy_(st['lr_dev'])
+    trainer.step_count = st['step_count']
+    if st['flags'] is not None:
+        trainer._lazy['flags'].copy_(st['flags'])
+        trainer._lazy['all_dirty'] = True
+    if st['fe_step'] is not None:
+        trainer.model.frontend.step = st['fe_step']  # (a copy into the counter the captured step reads)
+    tw = getattr(trainer.model, 'transformer', None)
+    if getattr(trainer, '_tower_shadow_attached', False) and hasattr(tw, 'mark_shadow_fresh'):
+        tw.mark_shadow_fresh()  # the restored S is the cast of the restored P
+
+
+def train_outputs(trainer, loss):
+    """What one training step hands back: the loss, the squared gradient norm clip_grad_norm_ saw, and the same seeded sample of
+    the flat fp32 master weights (after the Adam update) and of the flat gradient buffer.  Copied to the host at once."""
+    idx = torch.from_numpy(flat_sample_index(trainer.numel)).to(trainer.P.device)
+    return {'loss': loss.detach().double().reshape(1), 'grad_sqnorm': trainer._sq.detach().double().reshape(1),
+            'weights_sample': trainer.P.index_select(0, idx), 'grads_sample': trainer.G.index_select(0, idx)}
+
+
+def image_outputs(images):
+    """What a sampling call hands back: the decoded videos; past DUMP_LIMIT a fixed, seeded sample of their flat values."""
+    if images.numel() * 4 <= DUMP_LIMIT:
+        return {'images': images}
+    idx = torch.from_numpy(flat_sample_index(images.numel(), DUMP_LIMIT // 8)).to(images.device)
+    return {'images_sample': images.reshape(-1).index_select(0, idx)}
+
+
+def dump_outputs(dirname, arrays):
+    """Write each array as DIR/<name>.npy (float32, or float64 where it already is); at most DUMP_LIMIT bytes in all."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(a)
+        host[name] = np.ascontiguousarray(a.double().numpy() if a.dtype == torch.float64 else a.float().numpy())
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f'[bench] --dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit')
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    print(f'[bench] wrote {len(host)} output arrays ({total / 2**20:.1f} MiB) to {dirname}', file=sys.stderr, flush=True)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 PMC_KERNELS = {  # bench kernel family -> kernel-name prefixes in the rocprofv3 PMC summaries
@@ -277,6 +357,7 @@ def run_artv_sampling(args, device, rank, world):
         images = call()[0]
     fence()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, image_outputs(images)) if args.dump_outputs and rank == 0 else None
     if dist.is_initialized():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -337,6 +418,8 @@ def run_artv_sampling(args, device, rank, world):
            'artv_train_step': {'ms_per_step': train_ms, 'video_tokens_per_s': b * 1024 / (train_ms * 1e-3), 'per_gpu_batch': b,
                                'loss': float(loss.detach())},
            'image_checksum': float(images.float().mean())}
+    if dumped:
+        out['dumped_outputs'] = dumped
     print(json.dumps(out))
 
 
@@ -362,6 +445,7 @@ def run_bert_sampling(args, device, rank, world):
         images = call()[0]
     fence()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, image_outputs(images)) if args.dump_outputs and rank == 0 else None
     if dist.is_initialized():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -383,6 +467,8 @@ def run_bert_sampling(args, device, rank, world):
                         'peak': PEAK_BF16_TFLOPS, 'unit': 'TFLOP/s', 'frac': flops / per_call / 1e12 / PEAK_BF16_TFLOPS, 'traffic': None,
                         'tower_passes_per_video': passes, 'ms_per_tower_pass_of_the_batch': per_call * 1e3 / cfg['T']},
            'image_checksum': float(images.float().mean())}
+    if dumped:
+        out['dumped_outputs'] = dumped
     print(f"[bench] BERT sampling: {per_call * 1e3:.1f} ms per generate_images call of {b} videos = {out['value']:.0f} generated "
           f"video-tokens/s", file=sys.stderr, flush=True)
     print(json.dumps(out))
@@ -436,7 +522,9 @@ def main():
     ap.add_argument('--layers', type=int, default=12, help=argparse.SUPPRESS)  # debugging only; 12 = the model
     ap.add_argument('--dry-run', action='store_true', help='rank plumbing only (gloo, no GPU work): start the ranks, all-reduce '
                     'one scalar, print the JSON skeleton')
-    ap.add_argument('--no-exact', action='store_true', help="skip the extra legs that time the step with vae.strict = 'split' (index-exact) and 'mixed' (99.9 %)")
+    ap.add_argument('--no-exact', action='store_true', help="skip the extra legs that time the step with vae.strict = 'split' (index-exact) and 'mixed' (99.9 %%)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed to DIR/<name>.npy (rank 0; float32 / float64, at most 64 MB)')
     ap.add_argument('--strict', nargs='?', const='fp32', default=None, choices=['fp32', 'split', 'mixed'],
                     help="run the VQGAN encoder in an exact-index mode: 'fp32' (vae.strict = True, fp32 matrix pipe) or 'split' "
                     "(vae.strict = 'split': bf16-pair convolutions, 3 products each, on the bf16 pipe)")
@@ -447,6 +535,8 @@ def main():
         raise SystemExit(self_launch(args.gpus))
     if args.steps is None:
         args.steps = 2 if args.config == 5 else (3 if args.sample else 50)  # 50 graph replays = ~0.85 s timed
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # a GPU box exposes all 256 hardware threads but a cgroup quota of a few cores: keep torch's CPU pool small so that
     # incidental host ops never fan out over hundreds of spinning OpenMP threads (cpu_baseline() sets its own count)
@@ -512,6 +602,7 @@ def main():
     batch = synth_batch(B, 8, device, gen, visuals=1 if args.config == 4 else 0)
     fn = loss_fn(model, args.config)
     tok_per_sample = 512
+    init_state = train_state(trainer) if args.dump_outputs else None  # every rank: the exchange mixes their gradients
 
     # The step is replayed as ONE hipGraph at every world size (with torch.distributed the bucketed all-reduces are captured
     # inside it, between the backward chunks they overlap with).  The host only calls replay.
@@ -537,6 +628,13 @@ def main():
     t0 = time.perf_counter()
     host_s = 0.0  # time the host spends issuing the steps (it runs ahead of the GPU; ~= dt would mean host-bound)
     for i in range(args.steps):  # the timed region: exactly `steps` steps as the product runs them (one graph replay each)
+        if init_state is not None and i == args.steps - 1:  # --dump-outputs: the last step runs on the initial state, off the clock
+            fence()
+            tp = time.perf_counter()
+            restore_train_state(trainer, init_state)
+            fence()
+            t0 += time.perf_counter() - tp
+            init_state = None  # (frees the copies)
         th = time.perf_counter()
         if graphed is None or graphed.graph is None:
             loss = eager_step(trainer, fn, batch)
@@ -545,6 +643,8 @@ def main():
         host_s += time.perf_counter() - th
     fence()
     dt = time.perf_counter() - t0
+    # the last timed step's outputs, taken before the profiling step below updates the weights once more
+    dumped = dump_outputs(args.dump_outputs, train_outputs(trainer, loss)) if args.dump_outputs and rank == 0 else None
     # Per-kernel-family timing: HIP events around every launch need direct launches (they cannot be recorded inside a graph
     # replay), so PROF_STEPS extra steps of the SAME step run eagerly right after the timed region.  (They used to replace
     # every 10th timed step: an eagerly launched step is ~600 launches and 25-150 ms on a loaded host, which moved the
@@ -679,6 +779,8 @@ def main():
             out['gradient_exchange'] = comm
         if exact:
             out['exact_index_step'] = exact
+        if dumped:
+            out['dumped_outputs'] = dumped
         if world == 1 and args.config == 2 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(model)
         print(json.dumps(out))

@@ -8,15 +8,24 @@ import torch
 
 from conftest import ROOT
 
-VOCAB = os.environ.get('MMVID_BPE_VOCAB', '/root/reference/mmvid_pytorch/data/bpe_simple_vocab_16e6.txt')
-needs_vocab = pytest.mark.skipif(not os.path.exists(VOCAB), reason='the CLIP merge table is reference data and is not shipped here')
+GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 
 
-@needs_vocab
-def test_tokenizer_matches_reference_goldens():
+@pytest.fixture(scope='module')
+def vocab(tmp_path_factory):
+    """The reference's CLIP merge table as SimpleTokenizer reads it (header + the 48,894 merges it uses), unpacked from
+    tests/golden/bpe_merges.txt.xz (tools/make_golden_tokenizer.py)."""
+    import lzma
+    path = tmp_path_factory.mktemp('bpe') / 'bpe_simple_vocab_16e6.txt'
+    with lzma.open(os.path.join(GOLDEN, 'bpe_merges.txt.xz'), 'rb') as src:
+        path.write_bytes(src.read())
+    return str(path)
+
+
+def test_tokenizer_matches_reference_goldens(vocab):
     from mmvid_amd.data import SimpleTokenizer
-    g = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'tokenizer.json')))
-    tok = SimpleTokenizer(VOCAB)
+    g = json.load(open(os.path.join(GOLDEN, 'tokenizer.json')))
+    tok = SimpleTokenizer(vocab)
     assert tok.vocab_size == g['vocab_size'] == 49408 and len(tok.encoder) == 49408
     for r in g['rows']:
         ids = tok.encode(r['text'])
@@ -296,7 +305,8 @@ def test_vox_dataset_attr_modes(tmp_path):
 
 def test_vox_text_grammar():
     """mm_vox_celeb/pcfg.py restated (mmvid_amd/vox_text.py): sentence forms, attribute grouping, negated 'No_' labels, exclusive hair
-    colours.  (The attribute tables themselves are compared with the reference's module when it is importable.)"""
+    colours.  The attribute tables themselves are compared with the reference module's (tests/golden/vox_attr_tables.json,
+    tools/make_golden_tokenizer.py)."""
     import random
     import re
 
@@ -324,14 +334,9 @@ def test_vox_text_grammar():
     assert all(sum(m[vt.ATTR.index(a)] for a in vt.HAIR_COLOURS) == 1 for m in many)
     sents = vt.generate_random_sentences(8, 12, r)
     assert len(sents) == 12 and all('smiling' not in s and 'blurry' not in s and 'brown hair' not in s for s in sents)
-    ref_dir = '/root/reference/mm_vox_celeb'
-    if os.path.exists(os.path.join(ref_dir, 'pcfg.py')):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location('ref_pcfg', os.path.join(ref_dir, 'pcfg.py'))
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)
-        assert list(ref.ATTR) == vt.ATTR and list(ref.NAME) == vt.NAME and dict(ref.ATTR_VERB) == vt.ATTR_VERB
-        assert ref.NEGATE_IDX == vt.NEGATE_IDX and ref.GENDER_IDX == vt.GENDER_IDX
+    ref = json.load(open(os.path.join(GOLDEN, 'vox_attr_tables.json')))
+    assert ref['ATTR'] == vt.ATTR and ref['NAME'] == list(vt.NAME) and ref['ATTR_VERB'] == vt.ATTR_VERB
+    assert ref['NEGATE_IDX'] == vt.NEGATE_IDX and ref['GENDER_IDX'] == vt.GENDER_IDX
 
 
 # ------------------------------------------------------------------------------------------------ one file per video (loader.py)
