@@ -578,6 +578,27 @@ int mmvid_prof_begin(int stride);
 int mmvid_prof_enable(int on); /* pause / resume recording without resetting */
 int mmvid_prof_end(double* ms, int64_t* sampled, double* flops, int64_t* launches_total, int nclass);
 
+/* ---- OpenAI CLIP around the towers (csrc/clip.hip; mmvid_amd/clip_model.py).  Inference only.
+ * patchify: utils/utils.py:66-71 (F.interpolate nearest to R, (x - mean) / std) + clip_model.py:274 (conv1 as a GEMM operand).
+ *   frames fp32 [N,3,S,S] -> bf16 [N*(R/P)^2, 3*P*P], columns (c, ky, kx) = visual.conv1.weight.reshape(width, 3*P*P).
+ *   normalize=1: frames in [0, 1]; src = min(floor(dst * ((float)S / R)), S - 1) (ATen's nearest rule), then CLIP's mean / std.
+ *   normalize=0: frames already at R and normalised (S must equal R).  P a multiple of 8. */
+int mmvid_clip_patchify(const float* frames, int N, int S, int R, int P, int normalize, void* out_bf16, void* stream);
+/* clip_model.py:275-284: out [N,T,E] = ln_pre([class_emb | patch_feat rows of the frame] + pos[T,E]); patch_feat [N*(T-1), E]
+ * fp32 (the patch GEMM's result).  E a multiple of 256, at most 1024. */
+int mmvid_clip_image_assemble(const float* patch_feat, const float* class_emb, const float* pos, const float* ln_w,
+                              const float* ln_b, float eps, int N, int T, int E, float* out, void* stream);
+/* clip_model.py:400-403: out [B,L,E] = token_embedding[ids] + pos[L,E] (an id outside [0, vocab) reads row 0);
+ * pool_idx [B] int32 (may be NULL) = ids.argmax(-1), the first maximum (clip_model.py:411-412). */
+int mmvid_clip_text_embed(const int64_t* ids, int B, int L, const float* table, int64_t vocab, const float* pos, int E,
+                          float* out, int32_t* pool_idx, void* stream);
+/* clip_model.py:290-293 and 408-412: out [B,D] = LN(x[b, row_b]) @ proj [E,D] (row_b = rows[b], or 0 when rows is NULL),
+ * then divided by its L2 norm if l2norm (clip_model.py:420-424, utils/utils.py:81-82).  x [B,L,E] fp32; D <= 1024. */
+int mmvid_clip_pool_project(const float* x, int B, int L, int E, const int32_t* rows, const float* ln_w, const float* ln_b,
+                            float eps, const float* proj, int D, int l2norm, float* out, void* stream);
+/* utils/utils.py:83-84: out [B*T] = <img[b*T + t], txt[b]> (img [B*T,D], txt [B,D] fp32). */
+int mmvid_clip_pair_scores(const float* img, const float* txt, int B, int T, int D, float* out, void* stream);
+
 /* ---- hipGraph replay of the long launch sequences (mmvid_vqgan_run, mmvid_tower_forward / _backward): a
  * sequence seen twice with identical arguments (shapes, device pointers, stream) is captured once and replayed
  * afterwards.  Opt-in (option "graphs" = 1); bypassed while the profiler above is recording.

@@ -141,6 +141,11 @@ SIGNATURES = {
     'mmvid_prof_end': [P, P, P, P, I],
     'mmvid_rows_pack': [P, I64, I, P, I, P, P, P],
     'mmvid_rows_merge': [P, I64, I, P, P, I, P],
+    'mmvid_clip_patchify': [P, I, I, I, I, I, P, P],
+    'mmvid_clip_image_assemble': [P, P, P, P, P, F, I, I, I, P, P],
+    'mmvid_clip_text_embed': [P, I, I, P, I64, P, I, P, P, P],
+    'mmvid_clip_pool_project': [P, I, I, I, P, P, P, F, P, I, I, P, P],
+    'mmvid_clip_pair_scores': [P, P, I, I, I, P, P],
 }
 OTHER = {'mmvid_last_error': ([], c_char_p), 'mmvid_abi_version': ([], I), 'mmvid_device_count': ([], I),
          'mmvid_warp_params_bytes': ([], I), 'mmvid_gemm_dw_multi_fill': ([I, P, I], ctypes.c_double),

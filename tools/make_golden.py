@@ -9,7 +9,7 @@ layout), and the reference's outputs.  Run:
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [case ...]
 
 Cases: vq vqgan_tiny vqgan_full vqgan_full16 vqgan_full16_refinit tower tower12 bert_tiny bert_tiny_visual bert_negvc bert_negvc_visual bert_flm bert_flm_bottleneck artv_tiny mask_predict
-       frontend mask_predict_race
+       frontend mask_predict_race clip_vit2 clip_vit12
 """
 import json
 import os
@@ -793,11 +793,71 @@ def case_mask_predict_race():
                                                    b=dict(videos=1, steps=9, dynamic=True, B=1))), **res)
 
 
+CLIP_DESCRIPTIONS = [  # clip_vit*: one caption longer than the 77-token context (truncated), one whose largest id repeats, one empty
+    ' '.join(['the red cube moves to the left of the blue sphere while the green cylinder rotates slowly'] * 6),
+    'a person is talking, a person is talking',
+    '',
+]
+
+
+def _clip_case(name, layers, seed):
+    """OpenAI CLIP ViT-B/32 (clip_model.py:298-436) with `layers` layers in both towers, synthetic weights of `seed`, logit_scale at
+    its initial log(1/0.07): encode_image / encode_text / forward, utils/utils.py:62-85 clip_similarity (its own lines, .cuda() the
+    identity on this CPU-only host) and the ln_final token features of utils_train.py:264-274."""
+    import types
+    sys.modules.setdefault('ftfy', types.SimpleNamespace(fix_text=lambda t: t))
+    from mmvid_pytorch.tokenizer import SimpleTokenizer
+    from mmvid_pytorch.transformers.clip_model import CLIP
+    import utils.utils as ref_utils
+    from utils.utils import clip_similarity
+    ref_utils.F = torch.nn.functional  # utils/utils.py uses F without importing it (the drivers' namespace has it)
+    clip = CLIP(512, 224, layers, 768, 32, 77, 49408, 512, 8, layers)
+    man = load_synth(clip, seed)
+    with torch.no_grad():
+        clip.logit_scale.fill_(float(np.log(1 / 0.07)))
+    clip.eval()
+    clip.input_resolution = torch.tensor(224)  # the TorchScript archive's attributes that clip_similarity reads
+    clip.context_length = torch.tensor(77)
+    tok = SimpleTokenizer()
+    text = tok.tokenize(CLIP_DESCRIPTIONS, 77, truncate_text=True)
+    frames = synth_input('clip_frames128', (6, 3, 128, 128), seed, 'uniform')
+    frames224 = synth_input('clip_frames224', (2, 3, 224, 224), seed)  # already normalised: encode_image's own input
+    mean = torch.tensor([0.48145466, 0.4578275, 0.40821073])[:, None, None]
+    std = torch.tensor([0.26862954, 0.26130258, 0.27577711])[:, None, None]
+    pre = (torch.nn.functional.interpolate(frames, (224, 224)) - mean) / std
+    images = torch.cat([pre, frames224])
+    cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda t, *a, **k: t
+    try:
+        with torch.no_grad():
+            img = clip.encode_image(images)
+            txt = clip.encode_text(text)
+            lpi, lpt = clip(images, text)
+            x = clip.token_embedding(text) + clip.positional_embedding
+            feats = clip.ln_final(clip.transformer(x.permute(1, 0, 2)).permute(1, 0, 2))
+        sims = [clip_similarity(clip, tok, frames[3 * v:3 * v + 3], [CLIP_DESCRIPTIONS[v]]) for v in range(2)]
+    finally:
+        torch.Tensor.cuda = cuda
+    save(name, meta=dict(seed=seed, layers=layers, descriptions=CLIP_DESCRIPTIONS, logit_scale=float(np.log(1 / 0.07)),
+                         similarity='frames[3v:3v+3] against descriptions[v], v = 0, 1'),
+         manifest=man, text=text, encode_image=img, encode_text=txt, logits_per_image=lpi, logits_per_text=lpt,
+         similarity=np.stack(sims), token_features_s=feats[:, :, ::8], pool_index=text.argmax(-1))
+
+
+def case_clip_vit2():
+    _clip_case('clip_vit2', 2, 29)
+
+
+def case_clip_vit12():
+    _clip_case('clip_vit12', 12, 31)
+
+
 CASES = dict(vq=case_vq, vqgan_tiny=case_vqgan_tiny, vqgan_full=case_vqgan_full, vqgan_full16=case_vqgan_full16,
              vqgan_full16_refinit=case_vqgan_full16_refinit, tower=case_tower, tower12=case_tower12,
              bert_tiny=case_bert_tiny, bert_tiny_visual=case_bert_tiny_visual, bert_negvc=case_bert_negvc, bert_negvc_visual=case_bert_negvc_visual, bert_flm=case_bert_flm,
              bert_flm_bottleneck=case_bert_flm_bottleneck, artv_tiny=case_artv_tiny,
-             mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race)
+             mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race,
+             clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12)
 
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
