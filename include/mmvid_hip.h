@@ -35,7 +35,8 @@ int mmvid_gather_rows(const float* table, int64_t table_rows, const int64_t* idx
 /* ---- bf16 MFMA GEMM with fused epilogue: nn.Linear / MultiheadAttention projections,
  * clip_model.py:208-213,222 and dalle_bert.py:414-417 (+ their autograd backward GEMMs).
  *   C[m][n] = alpha * sum_k A(m,k) B(n,k)   A row-major [M][K] or k-major [K][M]; B row-major [N][K] or k-major [K][N]
- *   then: +bias[n]; save_pre<-bf16; act (1 = QuickGELU, clip_model.py:196-198); *QuickGELU'(dact_pre);
+ *   then: +bias[n]; save_pre<-bf16; act (1 = QuickGELU, clip_model.py:196-198; 2 = exact erf GELU 0.5 x (1 + erf(x / sqrt 2)) in
+ *         fp32, RoBERTa's intermediate.dense, forward only: not with dact_pre); *QuickGELU'(dact_pre);
  *         +residual[m][n]; (+= out_f32 if accumulate); store out_f32 and/or out_bf16.
  *   splitk > 1: K is split over blocks, fp32 atomicAdd into out_f32 (which must hold the base value).  * out_colsum (optional, batch 1, no split-K): [N] += column sums of the stored result -- the bias gradient of the
  * Linear whose output gradient this GEMM produces (fused instead of a separate pass over the result). */
@@ -598,6 +599,52 @@ int mmvid_clip_pool_project(const float* x, int B, int L, int E, const int32_t* 
                             float eps, const float* proj, int D, int l2norm, float* out, void* stream);
 /* utils/utils.py:83-84: out [B*T] = <img[b*T + t], txt[b]> (img [B*T,D], txt [B,D] fp32). */
 int mmvid_clip_pair_scores(const float* img, const float* txt, int B, int T, int D, float* out, void* stream);
+
+/* ---- RoBERTa-large, the frozen text encoder of --fixed_language_model roberta-large (csrc/roberta.hip; mmvid_amd/roberta.py).
+ * Inference only.  Replaces transformers' RobertaModel forward as utils/utils_train.py:194-222 / train.py:274-290 call it, and
+ * utils/utils.py:53-59 mean_pooling.
+ * embed: RobertaEmbeddings.forward with create_position_ids_from_input_ids -- position = pad_idx + (non-pad ids in [0, i]) for a
+ *   non-pad id at i, pad_idx for a pad id; x = LN(word[id] + type0 + pos[position]) (eps: the config's layer_norm_eps) -> x_f32
+ *   [B*L, E] and (optional) x_bf16; key_len [B] int32 = non-zero entries of mask [B, L] int64 (NULL: ids != pad_idx).  The mask must be
+ *   a prefix of each row (right padding): otherwise MMVID_ERR_ARG.  That test reads key_len back (one stream synchronisation) unless
+ *   the stream is being captured; under capture a bad row is left at key_len = -1.  E a multiple of 64, <= 1024; an id outside
+ *   [0, vocab) reads row 0. */
+int mmvid_roberta_embed(const int64_t* ids, const int64_t* mask, int B, int L, const float* word, int64_t vocab, const float* pos,
+                        int64_t npos, const float* type0, const float* ln_w, const float* ln_b, float eps, int E, int64_t pad_idx,
+                        float* x_f32, void* x_bf16, int32_t* key_len, void* stream);
+/* The attention core of mmvid_attention_fwd (same packed token-major Q|K|V layout, head_dim 64) with a per-sequence key-padding mask:
+ * keys >= key_len[b] (device int32 [B], clamped to [1, L]) are excluded for every query row -- transformers' additive finfo.min
+ * mask of RobertaSelfAttention -- and key tiles at or beyond key_len[b] are skipped.  Padded query rows get finite values (they attend
+ * to the live keys).  lse2 may be NULL. */
+int mmvid_attention_fwd_keylen(const void* qkv, int64_t ld, int B, int L, int H, int E, float scale, const int32_t* key_len, void* out,
+                               int64_t ldo, float* lse2, void* stream);
+/* The post-LN encoder layer loop (modeling_roberta.py RobertaLayer, all `layers` layers in one call), per layer on x [B*L, E] fp32:
+ *   qkv = x Wqkv^T + b (bf16 [3E, E], Q|K|V) -> key-length attention -> x1 = LN1(o Wo^T + bo + x)
+ *   -> h = gelu_erf(x1 W1^T + b1) (mmvid_gemm_bf16 act 2) -> x = LN2(h W2^T + b2 + x1).
+ * x_in_bf16 (optional): bf16(x_in), e.g. mmvid_roberta_embed's x_bf16 (NULL: cast here).  x_out may alias x_in.  scratch:
+ * mmvid_postln_encoder_workspace bytes.  No allocation, no host synchronisation (graph-capturable; "graphs" option as the tower). */
+typedef struct {
+    const void* qkv_w; /* [3E, E] bf16 */
+    const float* qkv_b; /* [3E] */
+    const void* out_w; /* [E, E] */
+    const float* out_b;
+    const float *ln1_w, *ln1_b;
+    const void* fc_w; /* [F, E] */
+    const float* fc_b;
+    const void* pj_w; /* [E, F] */
+    const float* pj_b;
+    const float *ln2_w, *ln2_b;
+} mmvid_postln_layer_t;
+typedef struct {
+    int B, L, E, H, F, layers;
+    float ln_eps;
+} mmvid_postln_cfg_t;
+int mmvid_postln_encoder_workspace(const mmvid_postln_cfg_t* cfg, int64_t* scratch_bytes);
+int mmvid_postln_encoder_forward(const mmvid_postln_cfg_t* cfg, const mmvid_postln_layer_t* layers, const int32_t* key_len,
+                                 const float* x_in, const void* x_in_bf16, float* x_out, void* scratch, void* stream);
+/* utils/utils.py:53-59: out [B, E] = (sum of the rows l of x [B, L, E] fp32 with mask[b][l] != 0) / max(count, 1e-9); the other rows
+ * are skipped, not multiplied by 0 (their contents need not be finite).  mask int64 [B, L]. */
+int mmvid_masked_mean_pool(const float* x, const int64_t* mask, int B, int L, int E, float* out, void* stream);
 
 /* ---- hipGraph replay of the long launch sequences (mmvid_vqgan_run, mmvid_tower_forward / _backward): a
  * sequence seen twice with identical arguments (shapes, device pointers, stream) is captured once and replayed

@@ -34,6 +34,15 @@ class DecodeToken(Structure):
                 ('logits_out', c_void_p), ('V', c_int32), ('e_pos0', c_int32), ('lnf_eps', c_float), ('temperature', c_float)]
 
 
+class PostLnLayer(Structure):
+    """mmvid_postln_layer_t (include/mmvid_hip.h)."""
+    _fields_ = [(n, P) for n in ('qkv_w', 'qkv_b', 'out_w', 'out_b', 'ln1_w', 'ln1_b', 'fc_w', 'fc_b', 'pj_w', 'pj_b', 'ln2_w', 'ln2_b')]
+
+
+class PostLnCfg(Structure):
+    _fields_ = [('B', I), ('L', I), ('E', I), ('H', I), ('F', I), ('layers', I), ('ln_eps', F)]
+
+
 class VqganOp(Structure):
     _fields_ = [('op', c_int32), ('mode', c_int32), ('N', c_int32), ('H', c_int32), ('W', c_int32), ('C', c_int32),
                 ('Cout', c_int32), ('flags', c_int32), ('in0', I64), ('in1', I64), ('in2', I64), ('out_bf16', I64),
@@ -146,6 +155,11 @@ SIGNATURES = {
     'mmvid_clip_text_embed': [P, I, I, P, I64, P, I, P, P, P],
     'mmvid_clip_pool_project': [P, I, I, I, P, P, P, F, P, I, I, P, P],
     'mmvid_clip_pair_scores': [P, P, I, I, I, P, P],
+    'mmvid_roberta_embed': [P, P, I, I, P, I64, P, I64, P, P, P, F, I, I64, P, P, P, P],
+    'mmvid_attention_fwd_keylen': [P, I64, I, I, I, I, F, P, P, I64, P, P],
+    'mmvid_postln_encoder_workspace': [POINTER(PostLnCfg), POINTER(I64)],
+    'mmvid_postln_encoder_forward': [POINTER(PostLnCfg), POINTER(PostLnLayer), P, P, P, P, P, P],
+    'mmvid_masked_mean_pool': [P, P, I, I, I, P, P],
 }
 OTHER = {'mmvid_last_error': ([], c_char_p), 'mmvid_abi_version': ([], I), 'mmvid_device_count': ([], I),
          'mmvid_warp_params_bytes': ([], I), 'mmvid_gemm_dw_multi_fill': ([I, P, I], ctypes.c_double),

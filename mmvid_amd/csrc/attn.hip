@@ -314,13 +314,18 @@ using ic = std::integral_constant<int, V>;
 // Three blocks per CU (round 6; four until then): at four the 128-register cap left 26 registers of the masked tile body in scratch -- the body
 // that runs for the tail tile and the two restricted rows of EVERY block.  154 registers, no scratch: 40.3 -> 38.0 us per layer at the training
 // shape, captured step 15.21 -> 15.12 ms, same box, alternating runs (profiles/r06_same_box_attention_forward_occupancy.log).
+// KEYLEN (mmvid_attention_fwd_keylen, RoBERTa's key-padding mask): sequence b has key_len[b] live keys, clamped to [1, L]; every key
+// expression below uses that count (Lk) and every query / addressing expression L, so tiles at or beyond it are neither staged nor
+// computed.  mask.mode is 0 there and lse2 may be null.  KEYLEN = false is the three-mode kernel exactly as before (Lk == L).
+template <bool KEYLEN>
 __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, long ld, int L, int H, int E, FastDiv nrt_d,
                                                            FastDiv h_d, float scale_log2, MaskSpec mask, bf16_t* __restrict__ out,
-                                                           long ldo, float* __restrict__ lse2) {
+                                                           long ldo, float* __restrict__ lse2, const int32_t* __restrict__ key_len) {
     __shared__ __attribute__((aligned(16))) char smem[2][2 * TILE];  // K tile, V tile, two stages
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l32 = lane & 31, h = lane >> 5;
     const BlockCoords bc = block_coords(nrt_d, h_d);
     const int qt = bc.rt, hd = bc.hd, b = bc.b;
+    const int Lk = KEYLEN ? min(max(key_len[b], 1), L) : L;  // live keys of this sequence
     const bf16_t* Kbase = qkv + (long)b * L * ld + E + hd * 64;
     const bf16_t* Vbase = Kbase + E;
     const RowLane rl = row_lane_offs(lane);
@@ -335,7 +340,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8_t*>(Qp + 16 * s + 8 * h);
     }
-    int kv_end = L;
+    int kv_end = Lk;
     if (mask.mode == 1) {
         const int blk_end = (qt + 1) * ROWS_PER_BLOCK;  // causal: the last key any of these queries may see, + 1
         if (blk_end < L) kv_end = blk_end;
@@ -343,7 +348,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
     const int t_begin = 0, t_end = (kv_end + 63) >> 6;
 
     TileStage stK, stV;
-    stK.init(Kbase, ld, L, wave, lane), stV.init(Vbase, ld, L, wave, lane);
+    stK.init(Kbase, ld, Lk, wave, lane), stV.init(Vbase, ld, Lk, wave, lane);
     stK.issue(t_begin * 64, smem[0], wave), stV.issue(t_begin * 64, smem[0] + TILE, wave);
 
     // running maximum (log2 domain, scaled), its negation as the exponent's reference (0 while it is -inf) and the raw-score value a
@@ -363,13 +368,13 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
     // own (lo at an even distance from t_begin: the LDS stage is a compile-time constant of each body); the tiles in front of and behind
     // that range run the general body.  (One loop with both bodies as alternatives made the register allocator give the accumulators
     // different homes on the two paths: 16 v_mov_b64 per tile at the join.)  Every tile of every wave passes exactly one barrier.
-    int lo = (row_kmax + 63) >> 6, hi = min(t_end - 1, L >> 6);
+    int lo = (row_kmax + 63) >> 6, hi = min(t_end - 1, Lk >> 6);
     if (mask.mode == 1) hi = min(hi, (q_wave0 + 1) >> 6);
     lo = max(lo, t_begin);
     lo += (lo - t_begin) & 1;
     if (lo >= t_end) lo = t_end;
     hi = hi > lo ? lo + ((hi - lo) & ~1) : lo;
-    const int kl0 = L - 4 * h;  // (padding mask: key0 + acc_row(r, 0) >= kl0 - key0)
+    const int kl0 = Lk - 4 * h;  // (padding mask: key0 + acc_row(r, 0) >= kl0 - key0)
 
     // one 64-key tile; ST = LDS stage (compile time: every fragment address is lane base + immediate), PLAIN = mask-free body
     auto tile = [&](auto st_c, auto plain_c, int t) {
@@ -385,7 +390,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
         // sub-tile's softmax arithmetic (VALU: exp2 is quarter rate) runs while the matrix pipe still works on the other
         // sub-tile's S or PV products.  Issued one sub-tile after the other (round 2), a wave sat in MFMA-result waits for 31 % of
         // its cycles and parked for 41 % (profiles/r03_pmc_attention_before_interleave.txt).
-        const bool two = PLAIN || t * 64 + 32 < L;  // the second sub-tile holds live keys (block-uniform)
+        const bool two = PLAIN || t * 64 + 32 < Lk;  // the second sub-tile holds live keys (block-uniform)
         f32x16 sv[2];
         auto s_mfmas = [&](auto ss_c) {
             constexpr int SS = decltype(ss_c)::value;
@@ -416,8 +421,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
                 // apply; otherwise, in the sub-tile that straddles L, the padding compare alone
                 if ((mask.mode == 1 && key0 + 31 > q_wave0) || key0 < row_kmax) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) s[r] = is_masked(mask, q, key0 + acc_row(r, h), L) ? -INFINITY : s[r];
-                } else if (key0 + 32 > L) {
+                    for (int r = 0; r < 16; ++r) s[r] = is_masked(mask, q, key0 + acc_row(r, h), Lk) ? -INFINITY : s[r];
+                } else if (key0 + 32 > Lk) {
                     mask_pad_keys(s, kl0 - key0);
                 }
             }
@@ -480,7 +485,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
     mfma_settle(oacc[0]), mfma_settle(oacc[1]);
     if (q < L) {  // (lanes l and l + 32 hold the same row: the half-wave exchange inside store_row64 pairs two active lanes)
         store_row64(out + ((long)b * L + q) * ldo + hd * 64, oacc, 1.0f / lsum, h);
-        if (h == 0) lse2[((long)b * H + hd) * L + q] = m_run + log2f(lsum);
+        if (h == 0 && (!KEYLEN || lse2)) lse2[((long)b * H + hd) * L + q] = m_run + log2f(lsum);
     }
 }
 
@@ -810,9 +815,27 @@ extern "C" int mmvid_attention_fwd(const void* qkv, int64_t ld, int B, int L, in
     const int nrt = cdiv(L, ROWS_PER_BLOCK), nblocks = nrt * H * B;
     const FastDiv nrt_d = make_fastdiv(nrt), h_d = make_fastdiv(H);
     const MaskSpec m = make_mask(mask_mode, r0, c0, r1, c1);
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, L, H, E, nrt_d, h_d,
-                       scale * 1.4426950408889634f, m, (bf16_t*)out, (long)ldo, lse2);
+    hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, L, H, E, nrt_d, h_d,
+                       scale * 1.4426950408889634f, m, (bf16_t*)out, (long)ldo, lse2, (const int32_t*)nullptr);
     MMVID_LAUNCH_CHECK("attention_fwd");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_attention_fwd_keylen(const void* qkv, int64_t ld, int B, int L, int H, int E, float scale, const int32_t* key_len,
+                                          void* out, int64_t ldo, float* lse2, void* stream) {
+    MMVID_REQUIRE(qkv && out && key_len, "attention_fwd_keylen: null pointer");
+    const int mask_mode = 0;
+    ATTN_COMMON_CHECKS("attention_fwd_keylen");
+    MMVID_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && ((uintptr_t)out & 15) == 0,
+                  "attention_fwd_keylen: leading dims must be multiples of 8, out 16-byte aligned");
+    MMVID_REQUIRE((int64_t)L * ld * 2 < (1ll << 31), "attention_fwd_keylen: one batch entry of qkv must be smaller than 2 GiB");
+    hipStream_t s = (hipStream_t)stream;
+    MmvidProfScope prof(PROF_ATTN_FWD, 4.0 * B * H * (double)L * L * 64, s);  // (an upper bound: padded keys are skipped)
+    const int nrt = cdiv(L, ROWS_PER_BLOCK), nblocks = nrt * H * B;
+    const FastDiv nrt_d = make_fastdiv(nrt), h_d = make_fastdiv(H);
+    hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, L, H, E, nrt_d, h_d,
+                       scale * 1.4426950408889634f, make_mask(0, -1, 0, -1, 0), (bf16_t*)out, (long)ldo, lse2, key_len);
+    MMVID_LAUNCH_CHECK("attention_fwd_keylen");
     return MMVID_OK;
 }
 

@@ -54,7 +54,7 @@ struct GemmParams {
     const bf16_t* dact_pre;  // [M][ldp] bf16: multiply by QuickGELU'(pre) (backward) or null
     bf16_t* save_pre;        // [M][ldp] bf16: store pre-activation (forward) or null
     long ldp;
-    int act;         // 0 none, 1 QuickGELU
+    int act;         // 0 none, 1 QuickGELU, 2 exact (erf) GELU
     int accumulate;  // out_f32 += result (non-atomic) when splitk == 1
     float alpha;     // scale applied to the accumulator first
     float* out_f32;  // [M][ldc] or null
@@ -79,6 +79,8 @@ __device__ __forceinline__ float sigmoid1702(float x) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x));
 }
 __device__ __forceinline__ float quick_gelu(float x) { return x * sigmoid1702(x); }
+// exact GELU, 0.5 x (1 + erf(x / sqrt 2)) in fp32 (transformers' ACT2FN['gelu'] = nn.GELU(): RoBERTa's intermediate.dense, forward only)
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float quick_gelu_grad(float x) {
     float s = sigmoid1702(x);
     return s * (1.0f + 1.702f * x * (1.0f - s));
@@ -161,6 +163,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, char* smem, f
             if (p.act == 1) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
+            } else if (p.act == 2) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
             }
             if (p.dact_pre) {
                 v[0] *= quick_gelu_grad(bf_lo(pre2[k].x));
@@ -337,6 +342,9 @@ __device__ __forceinline__ void pending_fill(const GemmParams& p, const BiasRegs
                 if (p.act == 1) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
+                } else if (p.act == 2) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
                 }
                 out[q] = u32x2_t{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
             }
@@ -738,9 +746,11 @@ void launch_shape(const GemmParams& p, int batch, hipStream_t stream) {
             pc.out_f32 = p.partial, pc.partial = nullptr, pc.accumulate = 0, pc.ldc = p.N, pc.strideC = (long)p.M * p.N, pc.strideA = 0,
             pc.strideB = 0, pc.splitk = 1;  // (for the eligibility test; the kernel gets splitk back below)
         }
-        if (direct_epilogue_ok((dact_packed || slabs) ? pc : p)) {
+        const bool packed = p.out_bf16 && !p.out_f32 && !p.residual && !p.dact_pre && !p.accumulate && p.N % 128 == 0 && batch == 1;
+        // (the erf GELU, act 2, lives in the packed and the LDS-slab epilogues only: the direct fp32 epilogue of the lw kernels is
+        //  shared with the grouped weight-gradient kernel, whose register budget it would cost)
+        if ((p.act != 2 || packed) && direct_epilogue_ok((dact_packed || slabs) ? pc : p)) {
             if (slabs) q.out_f32 = pc.out_f32, q.partial = nullptr, q.accumulate = 0, q.ldc = pc.ldc, q.strideC = pc.strideC, q.strideA = 0, q.strideB = 0;
-            const bool packed = p.out_bf16 && !p.out_f32 && !p.residual && !p.dact_pre && !p.accumulate && p.N % 128 == 0 && batch == 1;
             const int epi = dact_packed ? 4 : (packed ? (p.save_pre ? 3 : 2) : 1);
             const size_t lds = S::LDS_BYTES + BIAS_LDS_BYTES;
             static bool attr[5] = {false, false, false, false, false};
@@ -802,6 +812,8 @@ extern "C" int mmvid_gemm_bf16(int a_kmajor, int b_kmajor, int M, int N, int K, 
         const int64_t ea = a_kmajor ? (int64_t)K * lda : (int64_t)M * lda, eb = b_kmajor ? (int64_t)K * ldb : (int64_t)N * ldb;
         MMVID_REQUIRE(ea * 2 < (1ll << 31) && eb * 2 < (1ll << 31), "gemm_bf16: an operand of 2 GiB or more per batch entry");
     }
+    MMVID_REQUIRE(act >= 0 && act <= 2, "gemm_bf16: act %d (0 none, 1 QuickGELU, 2 erf GELU)", act);
+    MMVID_REQUIRE(!(act == 2 && dact_pre), "gemm_bf16: the erf GELU (act 2) is forward only: no dact_pre");
     if (splitk > 1)
         MMVID_REQUIRE(out_f32 && !out_bf16 && !act && !dact_pre && !save_pre && !residual && !out_colsum,
                       "gemm_bf16: split-K supports only fp32 atomic accumulation (+bias)");

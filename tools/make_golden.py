@@ -9,7 +9,7 @@ layout), and the reference's outputs.  Run:
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [case ...]
 
 Cases: vq vqgan_tiny vqgan_full vqgan_full16 vqgan_full16_refinit tower tower12 bert_tiny bert_tiny_visual bert_negvc bert_negvc_visual bert_flm bert_flm_bottleneck artv_tiny mask_predict
-       frontend mask_predict_race clip_vit2 clip_vit12
+       frontend mask_predict_race clip_vit2 clip_vit12 roberta_tokenizer roberta_tiny roberta_large24
 """
 import json
 import os
@@ -23,6 +23,9 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tools'))
 
 import torch  # noqa: E402
+
+if len(sys.argv) == 1 or any(c.startswith('roberta') for c in sys.argv[1:]):
+    import transformers  # noqa: E402,F401  (before the stubs: its import-time torchvision probe rejects the stub module)
 
 import ref_stubs  # noqa: E402
 from oracle.synth import synth_input, synth_state_dict, synth_tensor, synth_tokens  # noqa: E402
@@ -852,12 +855,141 @@ def case_clip_vit12():
     _clip_case('clip_vit12', 12, 31)
 
 
+# ---- RoBERTa (--fixed_language_model roberta-large): transformers' RobertaTokenizer / RobertaModel, the reference's own
+# utils/utils_train.py:194-222 get_fixed_language_model and utils/utils.py:53-59 mean_pooling
+ROBERTA_BPE = os.path.join(OUT, 'roberta_bpe')
+ROBERTA_SENTENCES = [  # the tokenizer fixture: empty, runs of spaces, contractions, digits, punctuation, non-ASCII, over-long
+    '',
+    'a person is talking',
+    '  two   spaces  and    four ',
+    "she's smiling, they're young and he'd like it; it's fine",
+    'a man with 5 o\'clock shadow, 1234 and 3.14159',
+    'Punctuation!? (yes) -- "quoted" [brackets] {braces} ...',
+    'caf\u00e9 na\u00efve \u00fcber \u65e5\u672c\u8a9e \U0001f600 r\u00e9sum\u00e9',
+    'this woman has wavy hair and big lips. she wears earrings and lipstick. ' * 6,
+    '\tTabs\nand newlines\r\n',
+]
+
+
+def _vox_corpus(n, seed):
+    from mmvid_amd.vox_text import generate_random_sentences
+    return generate_random_sentences(n_attr=8, n_sent=n, rng=random.Random(seed))
+
+
+def _learn_bpe(corpus, merges):
+    """Byte-level BPE merges learned from `corpus` with GPT-2's pre-tokenisation: most frequent adjacent pair first (ties: the
+    lexicographically smallest pair), `merges` of them."""
+    import regex
+    from collections import Counter
+    from mmvid_amd.roberta import PRETOKENIZE, bytes_to_unicode
+    be, pat = bytes_to_unicode(), regex.compile(PRETOKENIZE)
+    words = Counter(''.join(be[b] for b in piece.encode('utf-8')) for t in corpus for piece in pat.findall(t))
+    seqs = {w: list(w) for w in words}
+    out = []
+    for _ in range(merges):
+        pairs = Counter()
+        for w, c in words.items():
+            s = seqs[w]
+            for a, b in zip(s, s[1:]):
+                pairs[(a, b)] += c
+        if not pairs:
+            break
+        best = min(pairs, key=lambda p: (-pairs[p], p))
+        out.append(best)
+        for w in seqs:
+            s, i, n = seqs[w], 0, []
+            while i < len(s):
+                if i + 1 < len(s) and (s[i], s[i + 1]) == best:
+                    n.append(s[i] + s[i + 1])
+                    i += 2
+                else:
+                    n.append(s[i])
+                    i += 1
+            seqs[w] = n
+    return out
+
+
+def case_roberta_tokenizer():
+    """tests/golden/roberta_bpe/{vocab.json, merges.txt}: <s> <pad> </s> <unk>, the 256 byte symbols, the merges learned from the
+    vox_text caption grammar (at most 400: its corpus has 210), <mask>; roberta_tokenizer.npz: transformers' RobertaTokenizer on ROBERTA_SENTENCES (max_length 24)."""
+    from transformers import RobertaTokenizer
+    from mmvid_amd.roberta import bytes_to_unicode
+    merges = _learn_bpe(_vox_corpus(2000, 5), 400)
+    vocab = ['<s>', '<pad>', '</s>', '<unk>'] + sorted(bytes_to_unicode().values()) + [a + b for a, b in merges] + ['<mask>']
+    os.makedirs(ROBERTA_BPE, exist_ok=True)
+    with open(os.path.join(ROBERTA_BPE, 'vocab.json'), 'w', encoding='utf-8') as f:
+        json.dump({t: i for i, t in enumerate(vocab)}, f, ensure_ascii=False)
+    with open(os.path.join(ROBERTA_BPE, 'merges.txt'), 'w', encoding='utf-8') as f:
+        f.write('#version: 0.2\n' + ''.join(f'{a} {b}\n' for a, b in merges))
+    tok = RobertaTokenizer(os.path.join(ROBERTA_BPE, 'vocab.json'), os.path.join(ROBERTA_BPE, 'merges.txt'))
+    enc = tok(ROBERTA_SENTENCES, return_tensors='pt', padding=True, truncation=True, max_length=24)
+    full = tok(ROBERTA_SENTENCES, return_tensors='pt', padding=True)
+    save('roberta_tokenizer', meta=dict(sentences=ROBERTA_SENTENCES, max_length=24, vocab_size=len(vocab)),
+         input_ids=enc['input_ids'], attention_mask=enc['attention_mask'], input_ids_full=full['input_ids'],
+         attention_mask_full=full['attention_mask'])
+
+
+def _roberta_case(name, seed, **cfg):
+    """transformers' RobertaModel with synthetic weights of `seed`, driven through the reference's get_fixed_language_model(args)
+    .encode_text (its own lines: from_pretrained patched to return the local objects, .cuda() the identity on this CPU host)."""
+    import types
+    from transformers import RobertaConfig, RobertaModel, RobertaTokenizer
+    for mod in ('imageio', 'dominate', 'dominate.tags', 'dominate.util'):  # utils/utils_train.py's driver-side imports
+        sys.modules.setdefault(mod, types.ModuleType(mod))
+    sys.modules['dominate.tags'].__dict__.update({k: (lambda *a, **k: None) for k in ('meta', 'h1', 'h3', 'table', 'tr', 'td', 'p', 'a', 'img',
+                                                                                   'br')})
+    sys.modules['dominate'].document = lambda *a, **k: None
+    sys.modules['dominate.util'].raw = lambda *a, **k: None
+    import utils.utils_train as ut
+    tok = RobertaTokenizer(os.path.join(ROBERTA_BPE, 'vocab.json'), os.path.join(ROBERTA_BPE, 'merges.txt'))
+    config = RobertaConfig(max_position_embeddings=514, type_vocab_size=1, layer_norm_eps=1e-5, pad_token_id=1, bos_token_id=0,
+                           eos_token_id=2, hidden_act='gelu', **cfg)
+    model = RobertaModel(config, add_pooling_layer=True).eval()
+    man = load_synth(model, seed)
+    descriptions = _vox_corpus(5, seed) + ['', ROBERTA_SENTENCES[7]]
+    args = types.SimpleNamespace(fixed_language_model='roberta-large', text_seq_len=50)
+    cap = {}
+    model.register_forward_hook(lambda m, i, o: cap.update(h=o[0].detach().clone()))  # (returns None: the output stays)
+    rt, rm = transformers.RobertaTokenizer.from_pretrained, transformers.RobertaModel.from_pretrained
+    transformers.RobertaTokenizer.from_pretrained = classmethod(lambda cls, *a, **k: tok)
+    transformers.RobertaModel.from_pretrained = classmethod(lambda cls, *a, **k: model)
+    cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda t, *a, **k: t
+    model.cuda = lambda *a, **k: model
+    try:
+        tok2, lm, dim, encode_text = ut.get_fixed_language_model(args)
+        feats = encode_text(descriptions, device='cpu')
+    finally:
+        transformers.RobertaTokenizer.from_pretrained, transformers.RobertaModel.from_pretrained = rt, rm
+        torch.Tensor.cuda = cuda
+    enc = tok(descriptions, return_tensors='pt', padding=True, truncation=True, max_length=50)
+    h = cap['h']
+    save(name, meta=dict(seed=seed, config={k: getattr(config, k) for k in (
+        'vocab_size', 'hidden_size', 'num_hidden_layers', 'num_attention_heads', 'intermediate_size', 'hidden_act',
+        'max_position_embeddings', 'type_vocab_size', 'layer_norm_eps', 'pad_token_id')}, text_seq_len=50, descriptions=descriptions,
+        text_feature_dim=dim, hidden_subsample='last_hidden_state[:, :, ::8]'),
+         manifest=man, input_ids=enc['input_ids'], attention_mask=enc['attention_mask'], last_hidden_state_s=h[:, :, ::8],
+         pooled=feats)
+
+
+def case_roberta_tiny():
+    with open(os.path.join(ROBERTA_BPE, 'vocab.json'), encoding='utf-8') as f:
+        vocab_size = len(json.load(f))  # (the fixture's vocabulary: every id the tokenizer makes has a row)
+    _roberta_case('roberta_tiny', 41, vocab_size=vocab_size, hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=512)
+
+
+def case_roberta_large24():
+    _roberta_case('roberta_large24', 43, vocab_size=50265, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16,
+                  intermediate_size=4096)
+
+
 CASES = dict(vq=case_vq, vqgan_tiny=case_vqgan_tiny, vqgan_full=case_vqgan_full, vqgan_full16=case_vqgan_full16,
              vqgan_full16_refinit=case_vqgan_full16_refinit, tower=case_tower, tower12=case_tower12,
              bert_tiny=case_bert_tiny, bert_tiny_visual=case_bert_tiny_visual, bert_negvc=case_bert_negvc, bert_negvc_visual=case_bert_negvc_visual, bert_flm=case_bert_flm,
              bert_flm_bottleneck=case_bert_flm_bottleneck, artv_tiny=case_artv_tiny,
              mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race,
-             clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12)
+             clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12, roberta_tokenizer=case_roberta_tokenizer, roberta_tiny=case_roberta_tiny,
+             roberta_large24=case_roberta_large24)
 
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
