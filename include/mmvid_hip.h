@@ -646,6 +646,36 @@ int mmvid_postln_encoder_forward(const mmvid_postln_cfg_t* cfg, const mmvid_post
  * are skipped, not multiplied by 0 (their contents need not be finite).  mask int64 [B, L]. */
 int mmvid_masked_mean_pool(const float* x, const int64_t* mask, int B, int L, int E, float* out, void* stream);
 
+/* ---- I3D (RGB, Kinetics-400) for --eval_metric fvd_prd (csrc/i3d.hip; mmvid_amd/fvd.py).  Inference only.  Replaces the TF-Hub
+ * graph of utils/utils_eval.py:67-76,224-225 (frechet_video_distance.py:34-83 preprocess + create_id3_embedding).  Activations are
+ * NDHWC bf16; BatchNorm is folded into the weights (bf16) and an fp32 bias by the caller.
+ * conv3d: out = [relu](conv3d(x, w) + bias), x [N][T][H][W][Cin], w [Cout][kt][kh][kw][Cin]; front / back pads per dimension (TF
+ *   "SAME" is computed by the caller); output extents (T + p0 + p1 - k) / s + 1.  Output columns [seg_end[s-1], seg_end[s]) go to
+ *   out[s] at channels [c_off[s], +width) of rows ldo[s] wide (the Inception concat, or the three 1x1x1 branches of a block in one
+ *   launch).  Cin, Cout, segment widths, ldo, c_off multiples of 8; every tensor under 2 GiB.  Deterministic, batch-independent. */
+typedef struct {
+    int N, T, H, W, Cin, Cout;
+    int kt, kh, kw, st, sh, sw;
+    int pt0, pt1, ph0, ph1, pw0, pw1;
+    int relu, nseg;
+    int seg_end[3], ldo[3], c_off[3];
+    void* out[3];
+} mmvid_conv3d_t;
+int mmvid_conv3d_ndhwc(const mmvid_conv3d_t* cfg, const void* x, const void* w, const float* bias, void* stream);
+/* TF-SAME max pooling (padded taps ignored) of x [N][T][H][W][C] into channels [c_off, c_off + C) of rows ldo wide. */
+int mmvid_maxpool3d_ndhwc(const void* x, int N, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, int pt0,
+                          int pt1, int ph0, int ph1, int pw0, int pw1, void* out, int ldo, int c_off, void* stream);
+/* utils_eval.py:18-29,214-223 + frechet_video_distance.py:34-52: videos [n][t][3][h][w] fp32 in [0, 1] -> extend_video (ping-pong,
+ * when t < video_length) and cut to video_length frames -> x255 -> tf.image.resize_bilinear to 224^2 (TF1 legacy: align_corners and
+ * half_pixel_centers off) -> 2v/255 - 1, written as the stem operand: [n][video_length][224][112][24] bf16 with channel 3 kw + c of
+ * column wo = pixel (2 wo - 2 + kw, c) (zero outside the frame; channels 21..23 zero). */
+int mmvid_i3d_preprocess(const float* videos, int n, int t, int h, int w, int video_length, void* out, void* stream);
+/* the same stem operand from already preprocessed videos [n][t][224][224][3] fp32 */
+int mmvid_i3d_fold(const float* videos, int n, int t, void* out, void* stream);
+/* avgpool (2, 7, 7) VALID over x [N][To][7][7][C] bf16, logits = pooled w^T + b (w [ncls][C] fp32), mean over the To - 1 time steps
+ * -> out [N][ncls] fp32.  2 <= To <= 9, C <= 1024. */
+int mmvid_i3d_head(const void* x, int N, int To, int C, const float* w, const float* b, int ncls, float* out, void* stream);
+
 /* ---- hipGraph replay of the long launch sequences (mmvid_vqgan_run, mmvid_tower_forward / _backward): a
  * sequence seen twice with identical arguments (shapes, device pointers, stream) is captured once and replayed
  * afterwards.  Opt-in (option "graphs" = 1); bypassed while the profiler above is recording.

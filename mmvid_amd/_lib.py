@@ -43,6 +43,12 @@ class PostLnCfg(Structure):
     _fields_ = [('B', I), ('L', I), ('E', I), ('H', I), ('F', I), ('layers', I), ('ln_eps', F)]
 
 
+class Conv3dCfg(Structure):
+    """mmvid_conv3d_t (include/mmvid_hip.h)."""
+    _fields_ = [(n, I) for n in ('N', 'T', 'H', 'W', 'Cin', 'Cout', 'kt', 'kh', 'kw', 'st', 'sh', 'sw', 'pt0', 'pt1', 'ph0', 'ph1',
+                                 'pw0', 'pw1', 'relu', 'nseg')] + [('seg_end', I * 3), ('ldo', I * 3), ('c_off', I * 3), ('out', P * 3)]
+
+
 class VqganOp(Structure):
     _fields_ = [('op', c_int32), ('mode', c_int32), ('N', c_int32), ('H', c_int32), ('W', c_int32), ('C', c_int32),
                 ('Cout', c_int32), ('flags', c_int32), ('in0', I64), ('in1', I64), ('in2', I64), ('out_bf16', I64),
@@ -160,6 +166,11 @@ SIGNATURES = {
     'mmvid_postln_encoder_workspace': [POINTER(PostLnCfg), POINTER(I64)],
     'mmvid_postln_encoder_forward': [POINTER(PostLnCfg), POINTER(PostLnLayer), P, P, P, P, P, P],
     'mmvid_masked_mean_pool': [P, P, I, I, I, P, P],
+    'mmvid_conv3d_ndhwc': [POINTER(Conv3dCfg), P, P, P, P],
+    'mmvid_maxpool3d_ndhwc': [P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P],
+    'mmvid_i3d_preprocess': [P, I, I, I, I, I, P, P],
+    'mmvid_i3d_fold': [P, I, I, P, P],
+    'mmvid_i3d_head': [P, I, I, I, P, P, I, P, P],
 }
 OTHER = {'mmvid_last_error': ([], c_char_p), 'mmvid_abi_version': ([], I), 'mmvid_device_count': ([], I),
          'mmvid_warp_params_bytes': ([], I), 'mmvid_gemm_dw_multi_fill': ([I, P, I], ctypes.c_double),

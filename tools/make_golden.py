@@ -9,7 +9,7 @@ layout), and the reference's outputs.  Run:
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [case ...]
 
 Cases: vq vqgan_tiny vqgan_full vqgan_full16 vqgan_full16_refinit tower tower12 bert_tiny bert_tiny_visual bert_negvc bert_negvc_visual bert_flm bert_flm_bottleneck artv_tiny mask_predict
-       frontend mask_predict_race clip_vit2 clip_vit12 roberta_tokenizer roberta_tiny roberta_large24
+       frontend mask_predict_race clip_vit2 clip_vit12 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd
 """
 import json
 import os
@@ -983,13 +983,38 @@ def case_roberta_large24():
                   intermediate_size=4096)
 
 
+def case_fvd_prd():
+    """utils/utils_eval.py extend_video for t = 2, 4, 8 frames extended and cut as evaluate() does for VIDEO_LENGTH 15 / 16, and
+    precision_recall_distributions/prd_score.py compute_prd + prd_to_max_f_beta_pair on fixed histograms (pair 2 makes precision exceed
+    1 before the clip)."""
+    from utils.utils_eval import extend_video
+    import precision_recall_distributions.prd_score as prd
+    arrs = {}
+    for t in (2, 4, 8):
+        v = torch.arange(2 * t * 3 * 2 * 2, dtype=torch.float32).view(2, t, 3, 2, 2)
+        for vl in (15, 16):
+            num = int(np.ceil((vl - 1) / (t - 1)))
+            arrs[f'ext_t{t}_vl{vl}'] = extend_video(v, num)[:, :vl].numpy()
+    rng = np.random.RandomState(7)
+    hists = [(rng.dirichlet(np.ones(20)), rng.dirichlet(np.ones(20))),
+             (np.full(20, 0.05), np.full(20, 0.05)),
+             (np.array([0.5, 0.5005, 0., 0.]), np.array([0.5, 0.5, 0., 0.])),  # sums to 1.0005: clipped at 1
+             (np.array([1., 0., 0.]), np.array([0., 0.5, 0.5]))]
+    for i, (e, r) in enumerate(hists):
+        p, rc = prd.compute_prd(e, r)
+        arrs[f'prd{i}_eval'], arrs[f'prd{i}_ref'] = e, r
+        arrs[f'prd{i}_precision'], arrs[f'prd{i}_recall'] = p, rc
+        arrs[f'prd{i}_fbeta'] = np.array(prd.prd_to_max_f_beta_pair(p, rc))
+    save('fvd_prd_ref', meta=dict(n_hists=len(hists)), **arrs)
+
+
 CASES = dict(vq=case_vq, vqgan_tiny=case_vqgan_tiny, vqgan_full=case_vqgan_full, vqgan_full16=case_vqgan_full16,
              vqgan_full16_refinit=case_vqgan_full16_refinit, tower=case_tower, tower12=case_tower12,
              bert_tiny=case_bert_tiny, bert_tiny_visual=case_bert_tiny_visual, bert_negvc=case_bert_negvc, bert_negvc_visual=case_bert_negvc_visual, bert_flm=case_bert_flm,
              bert_flm_bottleneck=case_bert_flm_bottleneck, artv_tiny=case_artv_tiny,
              mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race,
              clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12, roberta_tokenizer=case_roberta_tokenizer, roberta_tiny=case_roberta_tiny,
-             roberta_large24=case_roberta_large24)
+             roberta_large24=case_roberta_large24, fvd_prd=case_fvd_prd)
 
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
