@@ -80,23 +80,21 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t n, FastDiv f) { return f.d == 
 
 // LDS-DMA of positions [p0, p0+64) x 64 d of one (batch, head) slice of a token-major matrix: 8 pieces of 1 KiB, 2 per
 // wave, through a buffer descriptor that ends at row L-1 -- positions >= L are zero-filled by the range check.
-// Per-lane offsets are computed once; a tile costs its two buffer_load ... lds and a scalar offset.
+// Wave w stages rows 8 w .. 8 w + 7 and 32 rows further: the swizzle does not see row bit 5, so both pieces share one per-lane
+// offset (computed once) and differ by a scalar offset only; a tile costs its two buffer_load ... lds and two scalar offsets.
 struct TileStage {
     rsrc_t rsrc;
-    uint32_t voff[2], rowbytes;
+    uint32_t voff, rowbytes;
     __device__ __forceinline__ void init(const bf16_t* slice, long ld, int L, int wave, int lane) {
         rsrc = make_rsrc(slice, (uint32_t)(((long)(L - 1) * ld + 64) * 2));
         rowbytes = (uint32_t)ld * 2u;
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) {
-            const int row = (wave * 2 + jj) * 8 + (lane >> 3);
-            const int chunk = (lane & 7) ^ swz(row);
-            voff[jj] = (uint32_t)row * rowbytes + (uint32_t)chunk * 16u;  // (L * ld * 2 < 2^31: checked by the launcher)
-        }
+        const int row = wave * 8 + (lane >> 3);
+        const int chunk = (lane & 7) ^ swz(row);
+        voff = (uint32_t)row * rowbytes + (uint32_t)chunk * 16u;  // (L * ld * 2 < 2^31: checked by the launcher)
     }
     __device__ __forceinline__ void issue(int p0, char* tile, int wave) const {
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj) blds16(rsrc, voff[jj], (uint32_t)p0 * rowbytes, tile + (wave * 2 + jj) * 1024);
+        blds16(rsrc, voff, (uint32_t)p0 * rowbytes, tile + wave * 1024);
+        blds16(rsrc, voff, (uint32_t)(p0 + 32) * rowbytes, tile + (wave + 4) * 1024);
     }
 };
 
@@ -643,12 +641,30 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
 }
 
 // ------------------------------------------------------------------------------------------ dK, dV
-constexpr int DKV_BUF = 2 * TILE + 512;  // Q tile, dO tile, lse2[64], delta[64]
+constexpr int DKV_BUF = 2 * TILE + 512;  // Q tile, dO tile, -lse2 / scale_log2 [64], -delta [64]
 
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, long ld, const bf16_t* __restrict__ dO, long lddo,
+// the initial accumulator of an S or dP chain: a per-query-row constant, 4 consecutive rows per float4 (rows 32 SS + acc_row(r, h))
+template <int SS>
+__device__ __forceinline__ f32x16 row_consts(const float* st, int h) {
+    f32x16 a;
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+        const float4 v = *reinterpret_cast<const float4*>(st + 32 * SS + 8 * g4 + 4 * h);
+        a[4 * g4] = v.x, a[4 * g4 + 1] = v.y, a[4 * g4 + 2] = v.z, a[4 * g4 + 3] = v.w;
+    }
+    return a;
+}
+
+// Three blocks per CU (168 registers, no scratch; two until round 7 at 212): the S -> softmax -> dV / dK chain of a sub-tile is
+// latency-bound, and a third wave per SIMD fills the matrix pipe while the other two wait on it.  Registers came from the row
+// constants: -lse2 / scale_log2 and -delta are the INITIAL ACCUMULATORS of the S and dP chains (S' = S - lse2 / scale_log2, dP' = dP -
+// delta: P = exp2(scale_log2 S'), dS = P dP' -- no row-constant registers beside the accumulators, no subtraction), and the Q^T
+// fragments are requested only once P and dS are packed.
+__global__ __launch_bounds__(256, 3) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, long ld, const bf16_t* __restrict__ dO, long lddo,
                                                                const float* __restrict__ lse2, const float* __restrict__ delta, int L, int H,
-                                                               int E, FastDiv nrt_d, FastDiv h_d, float scale, float scale_log2, MaskSpec mask,
-                                                               bf16_t* __restrict__ dqkv, long ldg, float* __restrict__ dbias) {
+                                                               int E, FastDiv nrt_d, FastDiv h_d, float scale, float scale_log2,
+                                                               float inv_scale_log2, MaskSpec mask, bf16_t* __restrict__ dqkv, long ldg,
+                                                               float* __restrict__ dbias) {
     __shared__ __attribute__((aligned(16))) char dsm[2][DKV_BUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l32 = lane & 31, h = lane >> 5;
     const BlockCoords bc = block_coords(nrt_d, h_d);
@@ -659,8 +675,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
     const float* del_b = delta + ((long)b * H + hd) * L;
     const int nq_tiles = (L + 63) >> 6;
     const RowLane rl = row_lane_offs(lane);
-    const TrLane tr0 = tr_lane_offs(lane);
-    const TrLane trq = tr_lane_at(tr0, lds_addr(dsm[0])), trdo = tr_lane_at(tr0, lds_addr(dsm[0] + TILE));
+    const TrLane trq = tr_lane_at(tr_lane_offs(lane), lds_addr(dsm[0]));  // Q tile of stage 0 (dO: + TILE, an immediate)
     const int key_wave0 = kt * ROWS_PER_BLOCK + wave * 32;
     const int key = key_wave0 + l32;
     const bool wave_active = key_wave0 < L;
@@ -675,13 +690,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
             vf[s] = *reinterpret_cast<const bf16x8_t*>(Vp + 16 * s + 8 * h);
         }
     }
-    // per-query statistics of a tile: threads 0..63 carry -lse2 (-inf for padded queries: exp2(-inf) = 0),
-    // threads 64..127 carry delta
+    // per-query row constants of a tile: threads 0..63 carry -lse2 / scale_log2 (-inf for padded queries: exp2(-inf) = 0),
+    // threads 64..127 carry -delta
     auto load_stat = [&](int t) -> float {
         if (tid >= 128) return 0.f;
         const int qq = t * 64 + (tid & 63);
-        if (tid < 64) return qq < L ? -lse_b[qq] : -INFINITY;
-        return qq < L ? del_b[qq] : 0.f;
+        if (tid < 64) return qq < L ? -lse_b[qq] * inv_scale_log2 : -INFINITY;
+        return qq < L ? -del_b[qq] : 0.f;
     };
     const int t_begin = (mask.mode == 1) ? (kt * ROWS_PER_BLOCK) >> 6 : 0, t_end = nq_tiles;  // causal: only queries >= keys contribute
 
@@ -703,7 +718,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
         const char* Qt = dsm[ST];
         const char* dOt = Qt + TILE;
         const float* st_nlse = reinterpret_cast<const float*>(Qt + 2 * TILE);
-        const float* st_del = st_nlse + 64;
+        const float* st_ndel = st_nlse + 64;
         char* nx = dsm[ST ^ 1];
         const bool more = t + 1 < t_end;
         dma_publish_barrier();
@@ -718,8 +733,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
         auto sub = [&](auto ss_c) {
             constexpr int SS = decltype(ss_c)::value;
             const int q0 = t * 64 + 32 * SS;
-            f32x16 s = mfma32z(row_frag<SS, 0>(Qt, rl), kf[0]);
-            f32x16 dp = mfma32z(row_frag<SS, 0>(dOt, rl), vf[0]);
+            f32x16 s = row_consts<SS>(st_nlse, h), dp = row_consts<SS>(st_ndel, h);
+            s = mfma32(row_frag<SS, 0>(Qt, rl), kf[0], s), dp = mfma32(row_frag<SS, 0>(dOt, rl), vf[0], dp);
             s = mfma32(row_frag<SS, 1>(Qt, rl), kf[1], s), dp = mfma32(row_frag<SS, 1>(dOt, rl), vf[1], dp);
             s = mfma32(row_frag<SS, 2>(Qt, rl), kf[2], s), dp = mfma32(row_frag<SS, 2>(dOt, rl), vf[2], dp);
             s = mfma32(row_frag<SS, 3>(Qt, rl), kf[3], s), dp = mfma32(row_frag<SS, 3>(dOt, rl), vf[3], dp);
@@ -729,9 +744,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
                 stat = load_stat(t + 1);
             }
             mfma_settle(s), mfma_settle(dp);
-            bf16x8_t dot4[4], qt4[4];  // dO^T and Q^T fragments, in consumption order
-            tr_frags4<SS, OFF>(trdo, dot4);
-            tr_frags4<SS, OFF>(trq, qt4);
+            bf16x8_t dot4[4];  // dO^T fragments: requested now, consumed after the softmax arithmetic
+            tr_frags4<SS, OFF + TILE>(trq, dot4);
             // mask needed?  (wave-uniform: the wave's keys are key_wave0 .. key_wave0 + 31) the causal diagonal region, or a restricted
             // query row among these queries AND some of this wave's keys below its bound
             bool nm = mask.mode == 1 && key_wave0 + 31 > q0;
@@ -740,24 +754,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[r] = is_masked(mask, q0 + acc_row(r, h), key, L) ? -INFINITY : s[r];
             }
-            const f32x2 sc2 = {scale_log2, scale_log2};
+            // P = exp2(scale_log2 S'), dS = P dP': single-lane v_mul_f32 in asm (-O3 would pack them; see exp2_affine_sum).  The exp is in
+            // the same statement: a VALU read of a v_exp_f32 result needs one wait state, which hipcc does not insert in front of asm
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int ql = 32 * SS + 8 * g4 + 4 * h;  // 4 consecutive query rows: registers 4 g4 .. 4 g4 + 3
-                const float4 l4 = *reinterpret_cast<const float4*>(st_nlse + ql);
-                const float4 d4 = *reinterpret_cast<const float4*>(st_del + ql);
-                f32x2 a = {s[4 * g4], s[4 * g4 + 1]}, c = {s[4 * g4 + 2], s[4 * g4 + 3]};
-                a = __builtin_elementwise_fma(a, sc2, (f32x2){l4.x, l4.y});
-                c = __builtin_elementwise_fma(c, sc2, (f32x2){l4.z, l4.w});
-                const float p0 = fast_exp2(a[0]), p1 = fast_exp2(a[1]), p2 = fast_exp2(c[0]), p3 = fast_exp2(c[1]);
-                s[4 * g4] = p0, s[4 * g4 + 1] = p1, s[4 * g4 + 2] = p2, s[4 * g4 + 3] = p3;
-                dp[4 * g4] = p0 * (dp[4 * g4] - d4.x);
-                dp[4 * g4 + 1] = p1 * (dp[4 * g4 + 1] - d4.y);
-                dp[4 * g4 + 2] = p2 * (dp[4 * g4 + 2] - d4.z);
-                dp[4 * g4 + 3] = p3 * (dp[4 * g4 + 3] - d4.w);
+            for (int r = 0; r < 16; ++r) {
+                float p, ds;
+                asm("v_mul_f32 %0, %2, %3\n\tv_exp_f32 %0, %0\n\ts_nop 0\n\tv_mul_f32 %1, %0, %4"
+                    : "=&v"(p), "=&v"(ds)
+                    : "v"(s[r]), "v"(scale_log2), "v"(dp[r]));
+                s[r] = p, dp[r] = ds;
             }
             bf16x8_t pf[2] = {pack_half(s, 0), pack_half(s, 1)};
             bf16x8_t dsf[2] = {pack_half(dp, 0), pack_half(dp, 1)};
+            bf16x8_t qt4[4];  // Q^T fragments: requested once s and dp are packed (16 registers fewer at the peak), under the dV MFMAs
+            tr_frags4<SS, OFF>(trq, qt4);
             lgkm_wait_tied<8>(dot4[0], dot4[1], dot4[2], dot4[3], pf[0], pf[1]);  // the 8 reads of Q^T may still be in flight
             dv[0] = mfma32(dot4[0], pf[0], dv[0]);
             dv[1] = mfma32(dot4[1], pf[0], dv[1]);
@@ -780,14 +790,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const bf16_t* __re
     }
     if (!wave_active) return;
     mfma_settle(dk[0]), mfma_settle(dk[1]), mfma_settle(dv[0]), mfma_settle(dv[1]);
-    if (key < L) {
-        bf16_t* kp = dqkv + ((long)b * L + key) * ldg + E + hd * 64;
-        store_row64(kp, dk, scale, h);
-        store_row64(kp + E, dv, 1.0f, h);
+    // the lane's coordinates afresh (v_mbcnt): values derived from them before the loop were kept in scratch across it
+    const int lane_e = (int)__lane_id(), key_e = key_wave0 + (lane_e & 31), h_e = lane_e >> 5;
+    if (key_e < L) {
+        bf16_t* kp = dqkv + ((long)b * L + key_e) * ldg + E + hd * 64;
+        store_row64(kp, dk, scale, h_e);
+        store_row64(kp + E, dv, 1.0f, h_e);
     }
     if (dbias) {
-        colsum_rows64(dk, scale, key < L, dbias + E + hd * 64, lane);
-        colsum_rows64(dv, 1.0f, key < L, dbias + 2 * E + hd * 64, lane);
+        colsum_rows64(dk, scale, key_e < L, dbias + E + hd * 64, lane_e);
+        colsum_rows64(dv, 1.0f, key_e < L, dbias + 2 * E + hd * 64, lane_e);
     }
 }
 
@@ -866,7 +878,7 @@ extern "C" int mmvid_attention_bwd_bias(const void* qkv, int64_t ld, const void*
     hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)O, (long)ldo,
                        (const bf16_t*)dO, (long)lddo, lse2, delta, L, H, E, nrt_d, h_d, scale, sl2, m, (bf16_t*)dqkv, (long)ldg, dbias);
     hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)dO, (long)lddo, lse2,
-                       delta, L, H, E, nrt_d, h_d, scale, sl2, m, (bf16_t*)dqkv, (long)ldg, dbias);
+                       delta, L, H, E, nrt_d, h_d, scale, sl2, 1.0f / sl2, m, (bf16_t*)dqkv, (long)ldg, dbias);
     MMVID_LAUNCH_CHECK("attention_bwd");
     return MMVID_OK;
 }
