@@ -4,19 +4,18 @@ kernels: same constructor, attributes (`image_size` is mutated by the driver, tr
 `model.encoder.* / model.decoder.* / model.quantize.embedding.weight / model.quant_conv.* / model.post_quant_conv.*`
 (taming/modules/diffusionmodules/model.py:363-582), so published `vqgan.1024.model.ckpt` files load.
 
-Execution (csrc/conv.hip, norm.hip, vq.hip): activations are NHWC; the residual stream is fp32, every conv
-input is bf16 (MFMA, fp32 accumulate); GroupNorm statistics are fp32.  The frozen weights are re-laid-out once
-into [Cout][ky][kx][Cin] bf16 (cached, refreshed when a parameter changes)."""
-from math import sqrt
-
+Execution (csrc/vqgan.hip, conv.hip, norm.hip, vq.hip): one encode / decode is an op list that vqgan_plan.py plans once per
+batch shape and arithmetic mode; this module keeps the parameters, the modes, and the caches of the plans and of the frozen
+weights re-laid-out into [Cout][ky][kx][Cin] (refreshed when a parameter changes)."""
 import os
+from math import sqrt
 
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import ops, vqgan_plan
 
-bf16, f32 = torch.bfloat16, torch.float32
+f32 = torch.float32
 
 # mmvid_pytorch/data/vqgan.1024.config.yml
 DEFAULT_DDCONFIG = dict(double_z=False, z_channels=256, resolution=256, in_channels=3, out_ch=3, ch=128,
@@ -132,337 +131,6 @@ class VQModel(_H):  # vqgan.py:16-53
         self.post_quant_conv = _conv(embed_dim, ddconfig['z_channels'], 1)
 
 
-# A/B switches for the planner's fusions (diagnostics; both on by default)
-_FUSE_GN = os.environ.get('MMVID_FUSE_GN', '1') != '0'
-_DUAL_OUT = os.environ.get('MMVID_DUAL_OUT', '1') != '0'
-_STRIP = os.environ.get('MMVID_CONV_STRIP', '1') != '0'
-_SPLITK = os.environ.get('MMVID_CONV_SPLITK', '1') != '0'
-_FUSE_QKV = os.environ.get('MMVID_FUSE_QKV', '1') != '0'  # AttnBlock q|k|v as one 1x1 conv (bf16 operator only)
-
-
-def _pow2_at_least8(c):
-    p = 8
-    while p < c:
-        p *= 2
-    return p
-
-
-class _Buf:
-    """Planned tensor: a byte range of the arena.  Dropping the last reference returns the range to the planner's
-    free list, which is exactly the liveness rule a single in-order stream needs."""
-
-    def __init__(self, pl, off, nbytes, shape, dtype):
-        self.pl, self.off, self.nbytes, self.shape, self.dtype = pl, off, nbytes, shape, dtype
-
-    def __del__(self):
-        if self.pl is not None and self.pl.recording:
-            self.pl.free.append((self.off, self.nbytes))
-
-
-class _Plan:
-    def __init__(self, ops_arr, arena, patches, kept):
-        self.ops, self.arena, self.patches, self.kept = ops_arr, arena, patches, kept
-
-    def run(self, ext_in, ext_out):
-        for i, field, name in self.patches:
-            src = ext_in if field == 'ext_in' else ext_out
-            setattr(self.ops[i], field, src[name].data_ptr())
-        _lib.call('mmvid_vqgan_run', self.ops, len(self.ops), ops._p(self.arena), ops._stream())
-
-
-class _Planner:
-    OP_IMG, OP_CONV, OP_GN, OP_CAST, OP_ATTN, OP_VQ, OP_GATHER, OP_NCHW, OP_EXT = range(9)
-    STRICT = 16  # MMVID_VQFLAG_STRICT: the fp32-accurate operator (csrc/strict.hip); all planned tensors are fp32
-    SPLIT = 64   # MMVID_VQFLAG_SPLIT: the bf16-pair operator; planned tensors are fp32 or pair planes [2][n,h,w,c] bf16
-    F16 = 128    # MMVID_VQFLAG_F16 (with SPLIT): a GroupNorm that writes one fp16 plane / the strip convolution that reads it
-
-    def __init__(self, vae, strict=False, stream16=False, f16_side=0):
-        self.vae, self.ops, self.free, self.top, self.recording = vae, [], [], 0, True
-        self.patches, self.kept = [], {}
-        self.split = strict == 'split'
-        # split operator only: 3x3 stride-1 convolutions on maps of at least f16_side x f16_side pixels that read a GroupNorm output run
-        # as ONE product of fp16 operands (vae.strict = 'mixed'); 0 = every convolution is the bf16-pair operator
-        self.f16_side = int(f16_side) if self.split else 0
-        self.strict = bool(strict) and not self.split
-        # bf16 operator only: the residual stream between blocks is stored as bf16 as well (no fp32 activation leaves a conv except
-        # the VQ rows and the decoded image); the exact operators keep their fp32 streams
-        self.stream16 = bool(stream16) and not self.strict and not self.split
-
-    # ---- split operator (vae.strict = 'split'): fp32 tensors between ops, every conv input a bf16 pair ----------------------
-    def _planes(self, x):
-        """fp32 tensor -> pair planes (a no-op for a tensor that already is one)."""
-        if getattr(x, 'is_planes', False):
-            return x
-        n, h, wd, c = x.shape
-        assert x.dtype == f32 and c % 8 == 0, x.shape
-        out = self.alloc((2, n, h, wd, c), bf16)
-        out.is_planes, out.shape = True, (n, h, wd, c)
-        self._op(op=self.OP_CAST, N=n, H=h, W=wd, C=c, flags=self.SPLIT, in0=x.off, out_bf16=out.off)
-        return out
-
-    def _conv_split(self, x, holder, mode, residual, clamp01, feeds_gn=False, planes_only=False):
-        x = self._planes(x)
-        w3, b, _ = self.vae._cw_split(holder)
-        n, h, wd, cin = x.shape
-        assert cin == w3.shape[3], (x.shape, w3.shape)
-        ho, wo = (h // 2, wd // 2) if mode == 1 else ((2 * h, 2 * wd) if mode == 2 else (h, wd))
-        cout = w3.shape[0]
-        assert residual is None or residual.dtype == f32
-        flags = self.SPLIT | (2 if clamp01 else 0)
-        scratch, ws = -1, None
-        strip = _STRIP and mode == 0 and not clamp01 and bool(_lib.load().mmvid_conv3x3_strip_supported(h, wd, cin, cout))
-        if strip:
-            flags |= 8
-        # planes_only: the result's only reader is another pair-operator convolution (a level's last tensor in front of its Downsample):
-        # the strip kernel's epilogue stores the bf16 pair itself -- no fp32 store, no cast pass (the same planes bit for bit)
-        planes_only = planes_only and strip and not feeds_gn
-        if planes_only:
-            out = self.alloc((2, n, ho, wo, cout), bf16)
-            out.is_planes, out.shape = True, (n, ho, wo, cout)
-        else:
-            out = self.alloc((n, ho, wo, cout), f32)
-        gn_op = getattr(x, 'gn_op', None)
-        if (strip and gn_op is not None and self.f16_side and min(h, wd) >= self.f16_side and holder.weight.shape[2] == 3
-                and getattr(x, 'pair_readers', 0) == 0):
-            # the fp16 form: this convolution is the FIRST reader of that GroupNorm's output (a residual block's norm -> conv), so the
-            # GroupNorm op already planned is switched to its fp16 output (first plane of the same buffer) and the weights are fp16
-            gn_op.flags |= self.F16
-            x.f16_plane = True
-            flags |= self.F16
-            w3 = self.vae._cw_f16(holder)[0]
-        else:  # a pair-plane reader: the buffer must still hold (hi, lo) planes, and no later reader may turn it into an fp16 plane
-            assert not getattr(x, 'f16_plane', False), 'a GroupNorm output switched to fp16 has a second reader that needs bf16 pairs'
-            if gn_op is not None:
-                x.pair_readers = getattr(x, 'pair_readers', 0) + 1
-        if feeds_gn and _FUSE_GN and (ho * wo) % 128 == 0 and cout % 128 == 0:  # the epilogue emits the GroupNorm partial sums
-            out.gn_stats = self._gn_stats(n, ho * wo, cout)
-            out.gn_stats.blocks64 = strip
-            flags |= 4
-            scratch = out.gn_stats.off
-        elif not strip and _SPLITK and mode == 0 and ho * wo <= 64 and 9 * cin >= 2304 and cout % 4 == 0:
-            ws = self.alloc((4 * n * ho * wo * cout, ), f32)
-            flags |= 32
-            scratch = ws.off
-        self._op(op=self.OP_CONV, mode=mode, N=n, H=h, W=wd, C=cin, Cout=cout, flags=flags, in0=x.off,
-                 in1=residual.off if residual is not None else -1, out_f32=-1 if planes_only else out.off,
-                 out_bf16=out.off if planes_only else -1, scratch=scratch, w=w3.data_ptr(), b=b.data_ptr())
-        del ws
-        return out
-
-    # arena allocation: first fit in the free list, else bump
-    def alloc(self, shape, dtype):
-        n = 1
-        for d in shape:
-            n *= d
-        nbytes = (n * (2 if dtype == bf16 else 4) + 255) // 256 * 256
-        for i, (off, sz) in enumerate(self.free):
-            if sz >= nbytes:
-                if sz > nbytes:
-                    self.free[i] = (off + nbytes, sz - nbytes)
-                else:
-                    self.free.pop(i)
-                return _Buf(self, off, nbytes, tuple(shape), dtype)
-        off = self.top
-        self.top += nbytes
-        return _Buf(self, off, nbytes, tuple(shape), dtype)
-
-    def _op(self, **kw):
-        o = _lib.VqganOp()
-        o.in0 = o.in1 = o.in2 = o.out_bf16 = o.out_f32 = o.scratch = -1
-        for k, v in kw.items():
-            setattr(o, k, v)
-        self.ops.append(o)
-        return len(self.ops) - 1
-
-    def image(self, n, s):
-        if self.split:
-            out = self.alloc((2, n, s, s, 8), bf16)
-            out.is_planes, out.shape = True, (n, s, s, 8)
-            i = self._op(op=self.OP_IMG, N=n, H=s, W=s, C=3, out_bf16=out.off, flags=self.SPLIT)
-            self.patches.append((i, 'ext_in', 'img'))
-            return out
-        if self.strict:
-            out = self.alloc((n, s, s, 4), f32)
-            i = self._op(op=self.OP_IMG, N=n, H=s, W=s, C=3, out_f32=out.off, flags=self.STRICT)
-            self.patches.append((i, 'ext_in', 'img'))
-            return out
-        out = self.alloc((n, s, s, 8), bf16)
-        i = self._op(op=self.OP_IMG, N=n, H=s, W=s, C=3, out_bf16=out.off)
-        self.patches.append((i, 'ext_in', 'img'))
-        return out
-
-    def conv(self, x, holder, mode, residual=None, out32=False, clamp01=False, feeds_gn=False, also_bf16=False, keep32=False):
-        """feeds_gn: a GroupNorm reads this output next -> the epilogue also emits its partial statistics (when the
-        shape allows), into a stats area that lives as long as the output buffer.
-        also_bf16 (with out32): the epilogue stores a bf16 copy too (`out.bf16`), instead of a later cast pass.
-        keep32: fp32 output even with a bf16 residual stream (the VQ rows, the decoded image)."""
-        if self.split:
-            return self._conv_split(x, holder, mode, residual, clamp01, feeds_gn, planes_only=not out32 and not keep32)
-        if self.stream16 and not keep32:
-            out32 = also_bf16 = False
-        w, b, _ = self.vae._cw(holder, self.strict)
-        n, h, wd, cin = x.shape
-        assert x.dtype == (f32 if self.strict else bf16) and cin == w.shape[2], (x.shape, w.shape)
-        ho, wo = (h // 2, wd // 2) if mode == 1 else ((2 * h, 2 * wd) if mode == 2 else (h, wd))
-        cout = w.shape[0]
-        if self.strict:
-            out = self.alloc((n, ho, wo, cout), f32)
-            self._op(op=self.OP_CONV, mode=mode, N=n, H=h, W=wd, C=cin, Cout=cout,
-                     flags=self.STRICT | (2 if clamp01 else 0), in0=x.off,
-                     in1=residual.off if residual is not None else -1, out_f32=out.off, w=w.data_ptr(), b=b.data_ptr())
-            return out
-        out = self.alloc((n, ho, wo, cout), f32 if out32 else bf16)
-        flags = (1 if (residual is not None and residual.dtype == f32) else 0) | (2 if clamp01 else 0)
-        # 3x3 stride-1 layers at 32x32 and above run in strip form (csrc/conv_strip.hip); the rule is geometry only
-        strip = _STRIP and mode == 0 and not clamp01 and bool(_lib.load().mmvid_conv3x3_strip_supported(h, wd, cin, cout))
-        if strip:
-            flags |= 8
-        scratch = -1
-        if feeds_gn and _FUSE_GN and (ho * wo) % 128 == 0 and cout % 128 == 0:
-            out.gn_stats = self._gn_stats(n, ho * wo, cout)
-            out.gn_stats.blocks64 = strip
-            flags |= 4
-            scratch = out.gn_stats.off
-        ws = None
-        if _SPLITK and not strip and scratch < 0 and mode == 0 and ho * wo <= 64 and 9 * cin >= 2304 and cout % 4 == 0:
-            # deep 3x3 layer on an 8x8 map: its 128x128 output tiles alone cover a fraction of the chip -> split-K by 4 through
-            # an fp32 workspace, fixed-order reduce (the rule is geometry only, like every kernel choice of the encoder)
-            ws = self.alloc((4 * n * ho * wo * cout, ), f32)
-            flags |= 32
-            scratch = ws.off
-        o16 = out.off if not out32 else -1
-        if out32 and also_bf16 and _DUAL_OUT:
-            out.bf16 = self.alloc((n, ho, wo, cout), bf16)
-            o16 = out.bf16.off
-        self._op(op=self.OP_CONV, mode=mode, N=n, H=h, W=wd, C=cin, Cout=cout, flags=flags, in0=x.off,
-                 in1=residual.off if residual is not None else -1, out_bf16=o16,
-                 out_f32=out.off if out32 else -1, scratch=scratch, w=w.data_ptr(), b=b.data_ptr())
-        del ws  # the workspace returns to the free list: later tensors of the plan may reuse it (one in-order stream)
-        return out
-
-    def _gn_stats(self, n, hw, c):
-        # per image: the per-channel affine [C][2], then partial sums [blocks][32][2] for blocks of 64 pixels (the strip
-        # convolution's granularity; 128-pixel producers use the first half)
-        return self.alloc((n * (2 * c + 64 * ((hw + 63) // 64)), ), f32)
-
-    def gn(self, x, holder, swish=True):
-        n, h, wd, c = x.shape
-        if self.split:
-            out = self.alloc((2, n, h, wd, c), bf16)
-            out.is_planes, out.shape = True, (n, h, wd, c)
-            st = getattr(x, 'gn_stats', None)  # partial sums already written by the producing convolution's epilogue
-            flags = self.SPLIT | (2 if st is not None else 0) | (8 if getattr(st, 'blocks64', False) else 0)
-            if st is None:
-                st = self._gn_stats(n, h * wd, c)
-            i = self._op(op=self.OP_GN, mode=int(swish), N=n, H=h, W=wd, C=c, flags=flags, in0=x.off, out_bf16=out.off,
-                         scratch=st.off, w=holder.weight.data_ptr(), b=holder.bias.data_ptr(), eps=1e-6)
-            out.gn_op = self.ops[i]  # (see _conv_split: its reader may switch it to the fp16 output)
-            return out
-        if self.strict:
-            out = self.alloc(x.shape, f32)
-            st = self.alloc((n * 2 * c, ), f32)
-            self._op(op=self.OP_GN, mode=int(swish), N=n, H=h, W=wd, C=c, flags=self.STRICT, in0=x.off, out_f32=out.off,
-                     scratch=st.off, w=holder.weight.data_ptr(), b=holder.bias.data_ptr(), eps=1e-6)
-            return out
-        out = self.alloc(x.shape, bf16)
-        st = getattr(x, 'gn_stats', None)
-        flags = (1 if x.dtype == f32 else 0) | (2 if st is not None else 0) | (8 if getattr(st, 'blocks64', False) else 0)
-        if st is None:
-            st = self._gn_stats(n, h * wd, c)
-        self._op(op=self.OP_GN, mode=int(swish), N=n, H=h, W=wd, C=c, flags=flags, in0=x.off,
-                 out_bf16=out.off, scratch=st.off, w=holder.weight.data_ptr(), b=holder.bias.data_ptr(), eps=1e-6)
-        return out
-
-    def cast(self, x):
-        if self.split:
-            return self._planes(x)
-        if x.dtype == bf16 or self.strict:
-            return x
-        if getattr(x, 'bf16', None) is not None:  # the producing conv already stored the bf16 copy
-            return x.bf16
-        out = self.alloc(x.shape, bf16)
-        n, h, wd, c = x.shape
-        self._op(op=self.OP_CAST, N=n, H=h, W=wd, C=c, in0=x.off, out_bf16=out.off)
-        return out
-
-    def conv_qkv(self, x, blk):
-        """AttnBlock q / k / v (model.py:159-178: three 1x1 convs of the same input) as ONE 1x1 conv with the three weights
-        stacked along Cout: one launch instead of three small ones.  Returns the [n, h, w, 3c] buffer (q, k, v are its column blocks)
-        and c."""
-        w, b = self.vae._cw_qkv(blk)
-        n, h, wd, cin = x.shape
-        c = w.shape[0] // 3
-        out = self.alloc((n, h, wd, 3 * c), bf16)
-        self._op(op=self.OP_CONV, mode=3, N=n, H=h, W=wd, C=cin, Cout=3 * c, flags=0, in0=x.off, in1=-1, out_bf16=out.off, out_f32=-1,
-                 scratch=-1, w=w.data_ptr(), b=b.data_ptr())
-        return out, c
-
-    def spatial_attention_fused(self, qkv, c):
-        n, h, wd, c3 = qkv.shape
-        hw = h * wd
-        out = self.alloc((n, h, wd, c), bf16)
-        sc = self.alloc((n * hw * hw * 3 // 2 + 64, ), f32)
-        self._op(op=self.OP_ATTN, N=n, H=h, W=wd, C=c, in0=qkv.off, in1=qkv.off + 2 * c, in2=qkv.off + 4 * c, out_bf16=out.off,
-                 scratch=sc.off, eps=float(c)**-0.5, pad=c3)
-        return out
-
-    def spatial_attention(self, q, k, v):
-        n, h, wd, c = q.shape
-        hw = h * wd
-        if self.strict or self.split:  # (split: q, k, v are fp32 conv outputs; the fp32 attention is 0.2 % of the encoder's work)
-            out = self.alloc(q.shape, f32)
-            sc = self.alloc((2 * n * hw * hw, ), f32)
-            self._op(op=self.OP_ATTN, N=n, H=h, W=wd, C=c, flags=self.STRICT, in0=q.off, in1=k.off, in2=v.off,
-                     out_f32=out.off, scratch=sc.off, eps=float(c)**-0.5)
-            return out
-        out = self.alloc(q.shape, bf16)
-        sc = self.alloc((n * hw * hw * 3 // 2 + 64, ), f32)
-        self._op(op=self.OP_ATTN, N=n, H=h, W=wd, C=c, in0=q.off, in1=k.off, in2=v.off, out_bf16=out.off,
-                 scratch=sc.off, eps=float(c)**-0.5)
-        return out
-
-    def vq_argmin(self, z):
-        n, h, wd, c = z.shape
-        cb = self.vae.model.quantize.embedding.weight
-        i = self._op(op=self.OP_VQ, N=n, H=h, W=wd, C=c, Cout=cb.shape[0], in0=z.off, w=cb.data_ptr(),
-                     b=self.vae._ee().data_ptr())
-        self.patches.append((i, 'ext_out', 'idx'))
-
-    def gather(self, n, hw):
-        cb = self.vae.model.quantize.embedding.weight
-        f32out = self.strict or self.split
-        out = self.alloc((n, hw, hw, cb.shape[1]), f32 if f32out else bf16)
-        i = self._op(op=self.OP_GATHER, N=n, H=hw, W=hw, C=cb.shape[1], Cout=cb.shape[0], w=cb.data_ptr(),
-                     flags=self.STRICT if f32out else 0, **{'out_f32' if f32out else 'out_bf16': out.off})
-        self.patches.append((i, 'ext_in', 'idx'))
-        return out
-
-    def external_z(self, n, hw, c):
-        """decode_train: z [n*hw*hw, c] fp32 computed outside the plan (probs @ codebook) enters here."""
-        f32out = self.strict or self.split
-        out = self.alloc((n, hw, hw, c), f32 if f32out else bf16)
-        i = self._op(op=self.OP_EXT, N=n, H=hw, W=hw, C=c, flags=self.STRICT if f32out else 0,
-                     **{'out_f32' if f32out else 'out_bf16': out.off})
-        self.patches.append((i, 'ext_in', 'z'))
-        return out
-
-    def to_nchw(self, x, cuse):
-        n, h, wd, c = x.shape
-        i = self._op(op=self.OP_NCHW, N=n, H=h, W=wd, C=c, Cout=cuse, in0=x.off)
-        self.patches.append((i, 'ext_out', 'img'))
-
-    def keep(self, name, buf):
-        """Pin a planned tensor so it can be read back after run() (tests / encode_z)."""
-        self.kept[name] = (buf.off, buf.shape)
-        self._pinned = getattr(self, '_pinned', []) + [buf]
-
-    def finish(self, device):
-        self.recording = False
-        arr = (_lib.VqganOp * len(self.ops))(*self.ops)
-        arena = torch.empty(max(self.top, 256), device=device, dtype=torch.uint8)
-        return _Plan(arr, arena, self.patches, self.kept)
-
-
 class VQGanVAE1024(nn.Module):
     def __init__(self, vae_path=None, image_size=None, ddconfig=None, n_embed=1024, embed_dim=256):
         super().__init__()
@@ -506,59 +174,13 @@ class VQGanVAE1024(nn.Module):
             self._prep_key = key
         return self._prep
 
-    def _cw(self, holder, strict=False):
-        """conv holder -> (w bf16 [Cout_p, taps, Cin_p], bias f32 [Cout_p], Cout); strict: w fp32 [Cout, taps, Cin_p4]."""
+    def _cw(self, holder, form='bf16'):
+        """conv holder -> (w [Cout_p, taps, Cin_p], bias f32 [Cout_p], Cout), the weights laid out for the kernels of one operator:
+        form = 'bf16' | 'f32' | 'pair' | 'f16' (vqgan_plan.conv_weights)."""
         prep = self._prepared()
-        k = (id(holder), strict)
-        if strict and k not in prep:
-            w, b = holder.weight.detach().float(), holder.bias.detach().float()
-            cout, cin, kh, kw = w.shape
-            cin_p = max(4, _pow2_at_least8(cin) if cin > 4 else 4)
-            wp = torch.zeros(cout, kh * kw, cin_p, device=w.device, dtype=f32)
-            wp[:, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
-            prep[k] = (wp.contiguous(), b.contiguous(), cout)
+        k = (id(holder), form)
         if k not in prep:
-            w, b = holder.weight.detach(), holder.bias.detach()
-            cout, cin, kh, kw = w.shape
-            cin_p, cout_p = _pow2_at_least8(cin), (cout + 7) // 8 * 8
-            wp = torch.zeros(cout_p, kh * kw, cin_p, device=w.device, dtype=f32)
-            wp[:cout, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
-            bp = torch.zeros(cout_p, device=w.device, dtype=f32)
-            bp[:cout] = b
-            prep[k] = (wp.to(bf16).contiguous(), bp, cout)
-        return prep[k]
-
-    def _cw_split(self, holder):
-        """conv holder -> (w3 bf16 [Cout_p, 3, taps, Cin_p] = (w_hi | w_hi | w_lo), bias f32 [Cout_p], Cout): the weight side of
-        the split operator, w = w_hi + w_lo with w_hi = bf16(w), w_lo = bf16(w - w_hi)."""
-        prep = self._prepared()
-        k = (id(holder), 'split')
-        if k not in prep:
-            w, b = holder.weight.detach().float(), holder.bias.detach().float()
-            cout, cin, kh, kw = w.shape
-            cin_p, cout_p = _pow2_at_least8(cin), (cout + 7) // 8 * 8
-            wp = torch.zeros(cout_p, kh * kw, cin_p, device=w.device, dtype=f32)
-            wp[:cout, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
-            hi = wp.to(bf16)
-            lo = (wp - hi.float()).to(bf16)
-            bp = torch.zeros(cout_p, device=w.device, dtype=f32)
-            bp[:cout] = b
-            prep[k] = (torch.stack([hi, hi, lo], 1).contiguous(), bp, cout)
-        return prep[k]
-
-    def _cw_f16(self, holder):
-        """conv holder -> (w fp16 [Cout_p, taps, Cin_p], bias f32 [Cout_p], Cout): the weight side of the fp16 single-product form."""
-        prep = self._prepared()
-        k = (id(holder), 'f16')
-        if k not in prep:
-            w, b = holder.weight.detach().float(), holder.bias.detach().float()
-            cout, cin, kh, kw = w.shape
-            cin_p, cout_p = _pow2_at_least8(cin), (cout + 7) // 8 * 8
-            wp = torch.zeros(cout_p, kh * kw, cin_p, device=w.device, dtype=f32)
-            wp[:cout, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
-            bp = torch.zeros(cout_p, device=w.device, dtype=f32)
-            bp[:cout] = b
-            prep[k] = (wp.to(torch.float16).contiguous(), bp, cout)
+            prep[k] = vqgan_plan.conv_weights(holder, form)
         return prep[k]
 
     def _cw_qkv(self, blk):
@@ -576,7 +198,7 @@ class VQGanVAE1024(nn.Module):
             prep['ee'] = ops.vq_sqnorm(self.model.quantize.embedding.weight.detach().contiguous())
         return prep['ee']
 
-    # ---- planning: the op sequence of one encode / decode for a given batch shape ------------------------------
+    # ---- planning: the op sequence of one encode / decode for a given batch shape (vqgan_plan.py), cached ------------------------
     def _plan(self, kind, n, size_or_hw, slot=0):
         prep = self._prepared()
         mode = 'split' if self.strict in ('split', 'mixed') else bool(self.strict)
@@ -585,91 +207,16 @@ class VQGanVAE1024(nn.Module):
         f16_side = self.mixed_f16_side if (self.strict == 'mixed' and kind == 'enc') else 0  # (the decoder stays the pair operator)
         key = ('plan', kind, n, size_or_hw, mode, slot, s16, f16_side)  # (slot: plans that run concurrently need arenas of their own)
         if key not in prep:
-            pl = _Planner(self, strict=mode, stream16=s16, f16_side=f16_side)
-            if kind == 'enc':
-                self._plan_encode(pl, n, size_or_hw)
-            elif kind == 'dec_z':
-                self._plan_decode(pl, n, size_or_hw, from_z=True)
+            if mode == 'split':
+                pl = vqgan_plan.PairPlanner(self, f16_side=f16_side)
             else:
-                self._plan_decode(pl, n, size_or_hw)
+                pl = vqgan_plan.StrictPlanner(self) if mode else vqgan_plan.Bf16Planner(self, stream16=s16)
+            if kind == 'enc':
+                vqgan_plan.plan_encode(pl, self.model, n, size_or_hw)
+            else:
+                vqgan_plan.plan_decode(pl, self.model, n, size_or_hw, from_z=kind == 'dec_z')
             prep[key] = pl.finish(next(self.model.parameters()).device)
         return prep[key]
-
-    def _plan_resblock(self, pl, x32, blk, final='f32'):
-        """model.py:130-150 on an fp32 residual stream.  final: 'f32' (residual stream continues), 'both' (a conv reads
-        the result next as well) or 'bf16' (ONLY a conv reads it: no fp32 store at all)."""
-        h = pl.conv(pl.gn(x32, blk.norm1), blk.conv1, 0, feeds_gn=True)
-        h = pl.gn(h, blk.norm2)
-        skip = x32
-        if hasattr(blk, 'nin_shortcut'):
-            skip = pl.conv(pl.cast(x32), blk.nin_shortcut, 3, out32=True)
-        return pl.conv(h, blk.conv2, 0, residual=skip, out32=final != 'bf16', feeds_gn=final != 'bf16',
-                       also_bf16=final == 'both')
-
-    def _plan_attn(self, pl, x32, blk, final='f32'):
-        """model.py:180-205."""
-        h = pl.gn(x32, blk.norm, swish=False)
-        if _FUSE_QKV and not pl.strict and not pl.split:
-            qkv, c = pl.conv_qkv(h, blk)
-            o = pl.spatial_attention_fused(qkv, c)
-        else:
-            q, k, v = pl.conv(h, blk.q, 3), pl.conv(h, blk.k, 3), pl.conv(h, blk.v, 3)
-            o = pl.spatial_attention(q, k, v)
-        return pl.conv(o, blk.proj_out, 3, residual=x32, out32=final != 'bf16', feeds_gn=final != 'bf16',
-                       also_bf16=final == 'both')
-
-    def _plan_encode(self, pl, n, s):
-        """Encoder.forward (model.py:439-466) + quant_conv (vqgan.py:67-68) + VQ lookup (quantize.py:302-310)."""
-        enc = self.model.encoder
-
-        def needs_bf16(blk):  # a resblock whose shortcut is a 1x1 conv reads its input in bf16 too
-            return hasattr(blk, 'nin_shortcut')
-
-        h = pl.conv(pl.image(n, s), enc.conv_in, 0, out32=True, feeds_gn=True, also_bf16=needs_bf16(enc.down[0].block[0]))
-        for li, d in enumerate(enc.down):
-            has_down = hasattr(d, 'downsample')
-            nxt = enc.down[li + 1].block[0] if li + 1 < len(enc.down) else enc.mid.block_1
-            for bi, blk in enumerate(d.block):
-                last = bi == len(d.block) - 1
-                with_attn = len(d.attn) > 0
-                # what the level's last tensor feeds: only the downsample conv (bf16) / the next block's shortcut too
-                end = 'bf16' if has_down else ('both' if needs_bf16(nxt) else 'f32')
-                mid = 'both' if (not last and needs_bf16(d.block[bi + 1])) else 'f32'
-                want = (end if last else mid) if _DUAL_OUT else 'f32'
-                h = self._plan_resblock(pl, h, blk, final='f32' if with_attn else want)
-                if with_attn:
-                    h = self._plan_attn(pl, h, d.attn[bi], final=want)
-            if has_down:
-                h = pl.conv(pl.cast(h), d.downsample.conv, 1, out32=True, feeds_gn=True, also_bf16=needs_bf16(nxt))
-        h = self._plan_resblock(pl, h, enc.mid.block_1)
-        h = self._plan_attn(pl, h, enc.mid.attn_1)
-        h = self._plan_resblock(pl, h, enc.mid.block_2)
-        h = pl.conv(pl.gn(h, enc.norm_out), enc.conv_out, 0)
-        z = pl.conv(h, self.model.quant_conv, 3, out32=True, keep32=True)  # [N, h, w, embed_dim] fp32 = VQ rows
-        pl.keep('z', z)
-        pl.vq_argmin(z)
-
-    def _plan_decode(self, pl, n, hw, from_z=False):
-        """codebook gather (vae.py:50) + post_quant_conv + Decoder.forward (model.py:551-582) + vae.py:55.
-        from_z: the quantised map arrives as an external fp32 tensor instead (decode_train, vae.py:58-68)."""
-        dec = self.model.decoder
-        z0 = pl.external_z(n, hw, self.model.quantize.embedding.weight.shape[1]) if from_z else pl.gather(n, hw)
-        h = pl.conv(z0, self.model.post_quant_conv, 3)
-        h = pl.conv(h, dec.conv_in, 0, out32=True, feeds_gn=True)
-        h = self._plan_resblock(pl, h, dec.mid.block_1)
-        h = self._plan_attn(pl, h, dec.mid.attn_1)
-        h = self._plan_resblock(pl, h, dec.mid.block_2)
-        for lvl in reversed(range(len(dec.up))):
-            u = dec.up[lvl]
-            for bi, blk in enumerate(u.block):
-                h = self._plan_resblock(pl, h, blk)
-                if len(u.attn) > 0:
-                    h = self._plan_attn(pl, h, u.attn[bi])
-            if hasattr(u, 'upsample'):
-                h = pl.conv(pl.cast(h), u.upsample.conv, 2, out32=True, feeds_gn=True)
-        h = pl.gn(h, dec.norm_out)
-        img = pl.conv(h, dec.conv_out, 0, out32=True, clamp01=True, keep32=True)  # (clamp(x,-1,1)+1)/2 fused, vae.py:55
-        pl.to_nchw(img, 3)
 
     # ---- reference API ------------------------------------------------------------------------------
     @torch.no_grad()

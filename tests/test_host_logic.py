@@ -371,12 +371,12 @@ def test_vqgan_plan_structure_config2(monkeypatch):
     graph; the q, k, v 1x1 convs of each of the 3 AttnBlocks are one launch with stacked weights), no cast passes
     (convs store the precisions their consumers read), GroupNorm statistics fused into the producing conv wherever
     the geometry allows, and a matching stats area on both sides of every fused pair."""
-    from mmvid_amd import vae as V
+    from mmvid_amd import vae as V, vqgan_plan as P
     v = V.VQGanVAE1024(None, 128)
     v.image_size = 128
     monkeypatch.setattr(v, '_ee', lambda: torch.zeros(1024))  # the codebook norms are a device kernel; not needed here
-    pl = V._Planner(v)
-    v._plan_encode(pl, 4, 128)
+    pl = P.Bf16Planner(v)
+    P.plan_encode(pl, v.model, 4, 128)
     ops_ = pl.ops
     kinds = [o.op for o in ops_]
     assert kinds.count(pl.OP_CONV) == 39 and kinds.count(pl.OP_CAST) == 0
@@ -403,13 +403,13 @@ def test_vqgan_plan_structure_config2(monkeypatch):
 def test_vqgan_plan_structure_split_mode(monkeypatch):
     """vae.strict = 'split': every convolution is the pair operator (flag 64) on pair planes and writes fp32; GroupNorm and the
     image layout write planes; attention is the fp32 operator; no bf16-operator op is left in the plan."""
-    from mmvid_amd import vae as V
+    from mmvid_amd import vae as V, vqgan_plan as P
     v = V.VQGanVAE1024(None, 128)
     v.image_size, v.strict = 128, 'split'
     monkeypatch.setattr(v, '_ee', lambda: torch.zeros(1024))
-    pl = V._Planner(v, strict='split')
+    pl = P.PairPlanner(v)
     assert pl.split and not pl.strict
-    v._plan_encode(pl, 4, 128)
+    P.plan_encode(pl, v.model, 4, 128)
     ops_ = pl.ops
     convs = [o for o in ops_ if o.op == pl.OP_CONV]
     assert len(convs) == 45 and all(o.flags & pl.SPLIT for o in convs)
@@ -423,7 +423,7 @@ def test_vqgan_plan_structure_split_mode(monkeypatch):
     assert sum(1 for o in convs if o.flags & 32) >= 4          # split-K on the 8x8 layers
     assert all(o.flags & pl.SPLIT for o in ops_ if o.op in (pl.OP_GN, pl.OP_CAST, pl.OP_IMG))
     assert all(o.flags & pl.STRICT for o in ops_ if o.op == pl.OP_ATTN)
-    w3, b, cout = v._cw_split(v.model.encoder.conv_in)
+    w3, b, cout = v._cw(v.model.encoder.conv_in, 'pair')
     assert w3.shape == (128, 3, 9, 8) and w3.dtype == torch.bfloat16 and cout == 128
     w = v.model.encoder.conv_in.weight.detach().permute(0, 2, 3, 1).reshape(128, 9, 3)
     assert torch.equal(w3[:, 0], w3[:, 1]) and (w3[:, 0, :, :3].float() + w3[:, 2, :, :3].float() - w).abs().max() < 2.0**-16
@@ -435,12 +435,12 @@ def test_vqgan_plan_structure_mixed_mode(monkeypatch):
     """vae.strict = 'mixed': the plan of 'split' with the F16 flag (128) on exactly the 3x3 residual-block convolutions of the 128x128,
     64x64 and 32x32 levels and on the GroupNorms that feed them -- 12 of the encoder's 45 convolutions, 82 % of its multiply-adds; the
     decoder's plan is the pair operator's."""
-    from mmvid_amd import vae as V
+    from mmvid_amd import vae as V, vqgan_plan as P
     v = V.VQGanVAE1024(None, 128)
     v.image_size, v.strict = 128, 'mixed'
     monkeypatch.setattr(v, '_ee', lambda: torch.zeros(1024))
-    pl = V._Planner(v, strict='split', f16_side=v.mixed_f16_side)
-    v._plan_encode(pl, 4, 128)
+    pl = P.PairPlanner(v, f16_side=v.mixed_f16_side)
+    P.plan_encode(pl, v.model, 4, 128)
     convs = [o for o in pl.ops if o.op == pl.OP_CONV]
     f16 = [o for o in convs if o.flags & pl.F16]
     assert len(convs) == 45 and len(f16) == 12 and all(o.flags & pl.SPLIT and o.flags & 8 and o.H >= 32 and o.C in (128, 256) for o in f16)
@@ -450,8 +450,43 @@ def test_vqgan_plan_structure_mixed_mode(monkeypatch):
     def work(o):
         return o.N * (o.H // (2 if o.mode == 1 else 1))**2 * o.Cout * o.C * (9 if o.mode in (0, 1, 2) else 1)
     assert 0.81 < sum(work(o) for o in f16) / sum(work(o) for o in convs) < 0.84
-    w16, b, cout = v._cw_f16(v.model.encoder.down[0].block[0].conv1)
+    w16, b, cout = v._cw(v.model.encoder.down[0].block[0].conv1, 'f16')
     assert w16.shape == (128, 9, 128) and w16.dtype == torch.float16 and cout == 128
-    pd = V._Planner(v, strict='split', f16_side=0)
-    v._plan_decode(pd, 2, 8)
+    pd = P.PairPlanner(v, f16_side=0)
+    P.plan_decode(pd, v.model, 2, 8)
     assert not any(o.flags & pd.F16 for o in pd.ops)
+
+
+def test_vqgan_weight_layouts_equal_the_plain_expression():
+    """The four encodings of a conv holder's weights (vae._cw) are permute to [Cout][ky*kx][Cin], zero-pad, cast -- for a 3x3 and a
+    1x1 layer, conv_in (Cin = 3) and the decoder's conv_out (Cout = 3); the stacked q | k | v weights are their concatenation."""
+    import torch.nn.functional as F
+    from mmvid_amd import vae as V
+    torch.manual_seed(0)
+    v = V.VQGanVAE1024(None, 128)
+    enc = v.model.encoder
+    blk = enc.down[2].block[0]  # 128 -> 256 channels: conv1 3x3, nin_shortcut 1x1
+    # holder, (Cin_p, Cout_p) of the bf16 / pair / fp16 forms, (Cin_p, Cout_p) of the fp32 form
+    for h, (cin_p, cout_p), (cin_p32, cout_p32) in ((blk.conv1, (128, 256), (128, 256)), (blk.nin_shortcut, (128, 256), (128, 256)),
+                                                    (enc.conv_in, (8, 128), (4, 128)), (v.model.decoder.conv_out, (128, 8), (128, 3))):
+        w, bias = h.weight.detach(), h.bias.detach()
+        cout, cin, kh, kw = w.shape
+
+        def plain(ci, co):
+            return (F.pad(w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin), (0, ci - cin, 0, 0, 0, co - cout)), F.pad(bias, (0, co - cout)))
+        wp, bp = plain(cin_p, cout_p)
+        hi = wp.to(torch.bfloat16)
+        want = {'bf16': hi, 'f16': wp.to(torch.float16), 'pair': torch.stack([hi, hi, (wp - hi.float()).to(torch.bfloat16)], 1)}
+        for form, ww in want.items():
+            got_w, got_b, got_cout = v._cw(h, form)
+            assert got_w.dtype == ww.dtype and got_w.is_contiguous() and torch.equal(got_w, ww), (form, tuple(w.shape))
+            assert got_b.dtype == torch.float32 and torch.equal(got_b, bp) and got_cout == cout
+        wp32, bp32 = plain(cin_p32, cout_p32)
+        got_w, got_b, got_cout = v._cw(h, 'f32')
+        assert got_w.dtype == torch.float32 and got_w.is_contiguous() and torch.equal(got_w, wp32)
+        assert torch.equal(got_b, bp32) and got_cout == cout
+        assert v._cw(h)[0] is v._cw(h, 'bf16')[0] and v._cw(h, 'pair')[0] is v._cw(h, 'pair')[0]  # cached, per form
+    a = enc.mid.attn_1
+    wq, bq = v._cw_qkv(a)
+    assert torch.equal(wq, torch.cat([v._cw(x)[0] for x in (a.q, a.k, a.v)])) and wq.shape == (1536, 1, 512)
+    assert torch.equal(bq, torch.cat([x.bias.detach() for x in (a.q, a.k, a.v)]))
