@@ -186,10 +186,10 @@ __global__ __launch_bounds__(256) void softmax_rows_f32_kernel(const float* __re
     for (int c = lane; c < cols; c += 64) dst[c] = expf(src[c] * scale - mx) / sum;
 }
 
-// GroupNorm(32) statistics in fp64: one block per (group, image) -> ab[n][C][2] = (rstd*w, b - mean*rstd*w)
+// GroupNorm(32) statistics in fp64: one block per (group, image) -> stats[n][C][2] = (mean, rstd) of the channel's group,
+// rounded to fp32 once at the end
 __global__ __launch_bounds__(256) void groupnorm_stats_f64_kernel(const float* __restrict__ x, long hw, int C, float eps,
-                                                                  const float* __restrict__ w, const float* __restrict__ b,
-                                                                  float* __restrict__ ab) {
+                                                                  float* __restrict__ stats) {
     __shared__ double red[2][256];
     const int grp = blockIdx.x, n = blockIdx.y, cpg = C >> 5;
     const float* base = x + (long)n * hw * C + grp * cpg;
@@ -213,15 +213,14 @@ __global__ __launch_bounds__(256) void groupnorm_stats_f64_kernel(const float* _
     const double rstd = 1.0 / sqrt(var + (double)eps);
     if ((int)threadIdx.x < cpg) {
         const int ch = grp * cpg + threadIdx.x;
-        // stored as (mean, rstd) pairs: the apply kernel evaluates ((x - mean) * rstd) * w + b like ATen does
-        *reinterpret_cast<float2*>(ab + ((long)n * C + ch) * 2) = make_float2((float)mean, (float)rstd);
+        // the apply kernel evaluates ((x - mean) * rstd) * w + b like ATen does
+        *reinterpret_cast<float2*>(stats + ((long)n * C + ch) * 2) = make_float2((float)mean, (float)rstd);
     }
-    (void)w, (void)b;
 }
 
 // y = swish?(((x - mean) * rstd) * w + b) in fp32 with expf; 4 channels per thread
 __global__ __launch_bounds__(256) void groupnorm_apply_f32_kernel(const float* __restrict__ x, long hw, int C,
-                                                                  const float* __restrict__ ab, const float* __restrict__ w,
+                                                                  const float* __restrict__ stats, const float* __restrict__ w,
                                                                   const float* __restrict__ b, int swish,
                                                                   float* __restrict__ y, long total_chunks) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -231,7 +230,7 @@ __global__ __launch_bounds__(256) void groupnorm_apply_f32_kernel(const float* _
     const long pix = t / cchunks;
     const int n = (int)(pix / hw);
     const float4 v = *reinterpret_cast<const float4*>(x + pix * C + cc * 4);
-    const float4* q = reinterpret_cast<const float4*>(ab + ((long)n * C + cc * 4) * 2);
+    const float4* q = reinterpret_cast<const float4*>(stats + ((long)n * C + cc * 4) * 2);  // (mean, rstd) x 4 channels
     const float4 q0 = q[0], q1 = q[1];
     const float4 w4 = *reinterpret_cast<const float4*>(w + cc * 4), b4 = *reinterpret_cast<const float4*>(b + cc * 4);
     float o[4] = {((v.x - q0.x) * q0.y) * w4.x + b4.x, ((v.y - q0.z) * q0.w) * w4.y + b4.y,
@@ -320,7 +319,7 @@ extern "C" int mmvid_groupnorm_swish_nhwc_f32(const float* x, int N, int64_t hw,
     MMVID_REQUIRE(C % 32 == 0 && C % 4 == 0 && C / 32 <= 256, "groupnorm_f32: C=%d unsupported", C);
     if (N == 0 || hw == 0) return MMVID_OK;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(groupnorm_stats_f64_kernel, dim3(32, N), dim3(256), 0, s, x, (long)hw, C, eps, w, b, stats_scratch);
+    hipLaunchKernelGGL(groupnorm_stats_f64_kernel, dim3(32, N), dim3(256), 0, s, x, (long)hw, C, eps, stats_scratch);
     const long chunks = (long)N * hw * (C / 4);
     hipLaunchKernelGGL(groupnorm_apply_f32_kernel, dim3(cdiv(chunks, 256)), dim3(256), 0, s, x, (long)hw, C, stats_scratch, w,
                        b, swish, y, chunks);

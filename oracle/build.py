@@ -3,14 +3,15 @@ import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, 'liboracle_vq.so')
+SO = os.path.join(HERE, 'liboracle_vq.so')  # vq_argmin.c + f32_chain.c (the name predates the second source)
+SOURCES = ['vq_argmin.c', 'f32_chain.c']
 
 
 def build(force=False):
-    src = os.path.join(HERE, 'vq_argmin.c')
-    if force or not os.path.exists(SO) or os.path.getmtime(SO) < os.path.getmtime(src):
+    srcs = [os.path.join(HERE, s) for s in SOURCES]
+    if force or not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(['gcc', '-O2', '-ffp-contract=off', '-fno-fast-math', '-shared', '-fPIC',
-                               src, '-o', SO, '-lm'])
+                               *srcs, '-o', SO, '-lm'])
     return SO
 
 
