@@ -126,6 +126,8 @@ int mmvid_groupnorm_swish_nhwc(const void* x, int x_is_bf16, int N, int64_t hw, 
  * qkv: token-major [B*L, ld] bf16 with Q at column 0, K at E, V at 2E (nn.MultiheadAttention packing).
  * K/V (and Q/dO in the backward) tiles are read from this layout directly; no transposed copies are needed.
  * mask_mode 0 none | 1 causal | 2 rows (r0: columns < c0 masked, r1: columns < c1 masked; use -1 for unused).
+ * Every query row must keep at least one visible key (c <= L - 1): the result of a row whose keys are all masked is undefined.
+ * Nothing outside the declared [B*L][width] windows is read into a result or written: rows of a key tile beyond B*L are not consumed.
  * lse2[b][h][q] = log2-domain log-sum-exp, consumed by the backward.  delta: fp32 [B,H,L] scratch. */
 int mmvid_attention_fwd(const void* qkv, int64_t ld, int B, int L, int H, int E, float scale, int mask_mode, int r0,
                         int c0, int r1, int c1, void* out, int64_t ldo, float* lse2, void* stream);
@@ -144,6 +146,9 @@ int mmvid_assemble_sequence(const float* const* tables, const int64_t* table_row
 int mmvid_assemble_sequence_bwd(float* const* grad_tables, const int64_t* table_rows, int ntables,
                                 const int64_t* ids, const int32_t* seg, const float* dx, int64_t B, int L, int E,
                                 float* dpos, int accumulate_dpos, void* stream);
+/* Cross entropy over the rows with select[row] != 0 (select NULL: every row).  A row with select[row] == 0 is SKIPPED, not multiplied
+ * by 0: neither its logits nor its target are read (they need not be finite or in range), lse[row] = 0 and its dlogits row is 0.
+ * loss_sum[0] += sum over the selected rows of lse - logit[target] (one fp32 atomic per row). */
 int mmvid_cross_entropy_fwd(const float* logits, int64_t ldl, const int64_t* target, const uint8_t* select,
                             int64_t rows, int V, float* lse, float* loss_sum, void* stream);
 int mmvid_cross_entropy_bwd(const float* logits, int64_t ldl, const int64_t* target, const uint8_t* select,
@@ -367,7 +372,8 @@ int mmvid_decode_embed_record(const int64_t* tok, const float* table, int64_t ta
                               const int32_t* pos_dev, int pos_off, int B, int E, float* x, int64_t* record, int64_t record_ld,
                               int record_pos0, void* stream);
 /* building blocks: append K|V rows of qkv [B*L, ldq] at positions pos..pos+L-1, and one-query attention over the
- * cached positions 0..pos (head_dim 64, Lmax <= 4096). */
+ * cached positions 0..pos (head_dim 64, Lmax <= 4096).  kv_store writes those rows of the cache only; attention_decode reads the Q
+ * part of its qkv rows and the cache rows 0..pos only (rows beyond pos need not be finite). */
 int mmvid_kv_store(const void* qkv, int64_t ldq, int B, int L, int E, const int32_t* pos_dev, int pos0, int Lmax,
                    void* cache, void* stream);
 int mmvid_attention_decode(const void* qkv, int64_t ldq, const void* cache, int B, int Lmax, int H, int E,
