@@ -181,7 +181,8 @@ int mmvid_rows_merge(float* W, int64_t V, int E, const int64_t* ids, const float
 
 /* Kernels never fault on a bad index: an embedding id outside its table reads row 0, a cross-entropy target outside [0, V)
  * counts as class 0 -- and both are COUNTED on the device (the reference's nn.Embedding / F.cross_entropy raise a device-side
- * assert instead).  counts[0] = bad embedding ids, counts[1] = bad CE targets, [2..3] reserved; reset != 0 clears them.
+ * assert instead).  counts[0] = bad embedding ids, counts[1] = bad CE targets, counts[2] = bad token-table rows
+ * (mmvid_token_rows_gather), [3] reserved; reset != 0 clears them.
  * Synchronises the device: call between steps, never during stream capture. */
 int mmvid_device_faults(int64_t* counts, int reset);
 
@@ -248,6 +249,24 @@ int mmvid_vid_warp_new_frames(uint64_t seed, const float* step_dev, const float*
                               void* stream);
 int mmvid_vid_warp_tokens(const int64_t* target_tok, const int64_t* new_frame_tok, const void* params, int B, int T, int n,
                           int64_t* out, void* stream);
+/* ---- training from a token cache (mmvid_amd/token_cache.py): the uint8 input side and the resident token table.
+ * frames_u8 [N, H, W, 3] uint8, as image decoders deliver it -> out [N, 3, H, W] fp32 = float(u8) / 255.0f (a correctly rounded
+ * division: the arithmetic of torchvision's ToTensor and of data._load_frame). */
+int mmvid_frames_u8_to_f32(const uint8_t* frames_u8, int N, int H, int W, float* out, void* stream);
+/* mmvid_vid_warp_new_frames on x_u8 [B, T, H, W, 3] uint8: same WarpParams, same Philox stream and call counter, same
+ * draw_params switch.  A pixel becomes u8 / 255 when it is loaded and the colour shift / affine bilinear sample run on those
+ * values in the fp32 kernel's operation order: new_frames [B, 3, H, W] is bit-identical to the fp32 kernel on x = u8 / 255. */
+int mmvid_vid_warp_new_frames_u8(uint64_t seed, const float* step_dev, const uint8_t* x_u8, int B, int T, int H, int W,
+                                 const float* strategy_prob, void* params_scratch, int draw_params, float* new_frames,
+                                 void* stream);
+/* Only the draw of mmvid_vid_warp[_new_frames] (same stream, same counter) into params_scratch: the strategies "frame of another
+ * sample" and "frame shuffle" need no pixels, mmvid_vid_warp_tokens builds their negative from the target's tokens alone. */
+int mmvid_vid_warp_draw(uint64_t seed, const float* step_dev, int B, int T, const float* strategy_prob, void* params_scratch,
+                        void* stream);
+/* table [table_rows, n] uint16 (a whole dataset's tokens, device resident), frame_index [rows] int64 -> out [rows, n] int64.
+ * An index outside [0, table_rows) reads row 0 and is counted: mmvid_device_faults counts[2]. */
+int mmvid_token_rows_gather(const uint16_t* table, int64_t table_rows, const int64_t* frame_index, int64_t rows, int n,
+                            int64_t* out, void* stream);
 /* visual-token erasing on token maps tok [B, Tv, f, f] int64, in place.  erase_codebook_face (dalle_bert.py:796-848):
  * one of `nchoice` (<= 4) alternatives is drawn per call from the cumulative probabilities; modes[i] 0 = untouched,
  * 1 = keep only boxes[i] = (r0, r1, c0, c1), 2 = erase the box; frame0_full leaves frame 0 untouched. */

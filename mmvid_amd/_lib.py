@@ -135,6 +135,10 @@ SIGNATURES = {
     'mmvid_vid_warp': [U64, P, P, I, I, I, I, I, P, P, I, P, P],
     'mmvid_vid_warp_new_frames': [U64, P, P, I, I, I, I, I, P, P, I, P, P],
     'mmvid_vid_warp_tokens': [P, P, P, I, I, I, P, P],
+    'mmvid_frames_u8_to_f32': [P, I, I, I, P, P],
+    'mmvid_vid_warp_new_frames_u8': [U64, P, P, I, I, I, I, P, P, I, P, P],
+    'mmvid_vid_warp_draw': [U64, P, I, I, P, P, P],
+    'mmvid_token_rows_gather': [P, I64, P, I64, I, P, P],
     'mmvid_erase_tokens_choice': [U64, P, I, P, P, P, I, I, I, I, I64, P, P],
     'mmvid_random_erase_tokens': [U64, P, I, I, I, F, F, F, F, F, I, I64, P, P],
     'mmvid_visual_color_jitter': [U64, P, P, I, I, I, I, I, F, I, P, P],
@@ -237,7 +241,7 @@ def call(name, *args):
         raise MMVIDError(f'{name} failed (rc={rc}): {lib.mmvid_last_error().decode()}')
 
 
-FAULT_NAMES = ('embedding id outside its table', 'cross-entropy target outside [0, V)', 'reserved', 'reserved')
+FAULT_NAMES = ('embedding id outside its table', 'cross-entropy target outside [0, V)', 'token-table row outside its table', 'reserved')
 
 
 def device_faults(reset=True):

@@ -114,3 +114,5 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // the record, and the comments next to the surviving code say what was measured against it.
 enum { MMVID_OPT_GRAPHS = 0, MMVID_OPT_COUNT = 1 };
 int mmvid_option(int which);  // errors.hip
+// embed.hip: the device fault counters behind mmvid_device_faults() ([0] embedding ids, [1] cross-entropy targets, [2] token-table rows)
+unsigned long long* mmvid_fault_counters_dev();

@@ -20,7 +20,8 @@ struct GradTables {
 
 // Device-side fault counters: kernels never fault on bad indices (an out-of-range id reads row 0), they COUNT them;
 // mmvid_device_faults() reads and optionally clears the counters (a synchronising call: between steps, not during capture).
-//   [0] embedding id outside its table (assemble_sequence), [1] cross-entropy target outside [0, V)
+//   [0] embedding id outside its table (assemble_sequence), [1] cross-entropy target outside [0, V),
+//   [2] token-table row outside its table (frontend.hip: token_rows_gather, through mmvid_fault_counters_dev)
 __device__ unsigned long long g_faults[4];
 
 // one wave per (b,l) row; E % 4 == 0
@@ -570,4 +571,18 @@ extern "C" int mmvid_device_faults(int64_t* counts, int reset) {
         }
     }
     return MMVID_OK;
+}
+
+// Device address of the fault counters for kernels of other translation units (common.h).  Resolved once per device: later
+// calls, a call during stream capture included, only read the cached pointer.
+unsigned long long* mmvid_fault_counters_dev() {
+    static unsigned long long* cache[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    if (!cache[dev]) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_faults)) != hipSuccess) return nullptr;
+        cache[dev] = (unsigned long long*)p;
+    }
+    return cache[dev];
 }

@@ -211,7 +211,10 @@ __device__ __forceinline__ float reflect_coord(float in, float twice_low, float 
 }
 
 // F.affine_grid(theta, size, align_corners=False) + F.grid_sample(bilinear, padding_mode='reflection', align_corners=False)
-__device__ __forceinline__ float affine_sample(const float* __restrict__ img, int H, int W, const float* th, int y, int x) {
+// `px(i)` = pixel i of the source plane: an fp32 load, or a uint8 load converted at load time (warp_new_frame_u8_kernel) -- one body,
+// so both sources go through the same operations in the same order.
+template <class Px>
+__device__ __forceinline__ float affine_sample_px(Px px, int H, int W, const float* th, int y, int x) {
     const float xn = (2.f * x + 1.f) / (float)W - 1.f, yn = (2.f * y + 1.f) / (float)H - 1.f;
     const float gx = th[0] * xn + th[1] * yn + th[2], gy = th[3] * xn + th[4] * yn + th[5];
     float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
@@ -221,11 +224,14 @@ __device__ __forceinline__ float affine_sample(const float* __restrict__ img, in
     const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
     const float wx1 = ix - x0f, wy1 = iy - y0f, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
     float v = 0.f;
-    if (x0 >= 0 && x0 < W && y0 >= 0 && y0 < H) v += img[y0 * W + x0] * wx0 * wy0;
-    if (x1 >= 0 && x1 < W && y0 >= 0 && y0 < H) v += img[y0 * W + x1] * wx1 * wy0;
-    if (x0 >= 0 && x0 < W && y1 >= 0 && y1 < H) v += img[y1 * W + x0] * wx0 * wy1;
-    if (x1 >= 0 && x1 < W && y1 >= 0 && y1 < H) v += img[y1 * W + x1] * wx1 * wy1;
+    if (x0 >= 0 && x0 < W && y0 >= 0 && y0 < H) v += px(y0 * W + x0) * wx0 * wy0;
+    if (x1 >= 0 && x1 < W && y0 >= 0 && y0 < H) v += px(y0 * W + x1) * wx1 * wy0;
+    if (x0 >= 0 && x0 < W && y1 >= 0 && y1 < H) v += px(y1 * W + x0) * wx0 * wy1;
+    if (x1 >= 0 && x1 < W && y1 >= 0 && y1 < H) v += px(y1 * W + x1) * wx1 * wy1;
     return v;
+}
+__device__ __forceinline__ float affine_sample(const float* __restrict__ img, int H, int W, const float* th, int y, int x) {
+    return affine_sample_px([img](int i) { return img[i]; }, H, W, th, y, x);
 }
 
 // x, out: [B, T, C, H, W] fp32.  One thread per output pixel.
@@ -283,6 +289,95 @@ __global__ __launch_bounds__(256) void warp_new_frame_kernel(const float* __rest
     }
     out[idx] = v;
 }
+// ---- uint8 input side (training from a token cache: mmvid_amd/token_cache.py).  Image decoders deliver [H, W, 3] bytes; the
+// data path turns them into floats as torchvision's ToTensor does: float(u8) / 255 -- a correctly rounded DIVISION (a multiply
+// by 1/255 differs in the last bit for some of the 256 values).
+__device__ __forceinline__ float u8_unit(unsigned v) { return __fdiv_rn((float)v, 255.0f); }
+
+struct U3 {
+    uint32_t a, b, c;
+};
+// in [N, HW, 3] uint8 -> out [N, 3, HW] fp32.  VEC: HW % 4 == 0 and `in` 4-byte aligned -- a thread converts 4 pixels: 12
+// contiguous bytes in (a wave reads 768 contiguous bytes), one float4 out per channel plane (a wave writes 1 KiB runs).
+template <bool VEC>
+__global__ __launch_bounds__(256) void frames_u8_to_f32_kernel(const unsigned char* __restrict__ in, long N, long HW,
+                                                               float* __restrict__ out) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        const long q = HW >> 2;  // groups of 4 pixels per frame
+        if (idx >= N * q) return;
+        const long n = idx / q, g = idx - n * q;
+        const U3 w = *reinterpret_cast<const U3*>(in + (n * HW + 4 * g) * 3);
+        const unsigned by[12] = {w.a & 255u, (w.a >> 8) & 255u, (w.a >> 16) & 255u, w.a >> 24, w.b & 255u, (w.b >> 8) & 255u,
+                                 (w.b >> 16) & 255u, w.b >> 24, w.c & 255u, (w.c >> 8) & 255u, (w.c >> 16) & 255u, w.c >> 24};
+        float* dst = out + n * 3 * HW + 4 * g;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            *reinterpret_cast<float4*>(dst + c * HW) =
+                make_float4(u8_unit(by[c]), u8_unit(by[3 + c]), u8_unit(by[6 + c]), u8_unit(by[9 + c]));
+    } else {
+        if (idx >= N * HW) return;
+        const long n = idx / HW, p = idx - n * HW;
+        const unsigned char* src = in + idx * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[(n * 3 + c) * HW + p] = u8_unit(src[c]);
+    }
+}
+
+// warp_new_frame_kernel on uint8 frames x [B, T, H, W, 3]: a pixel becomes u8 / 255 when it is loaded, everything after that is
+// the fp32 kernel's arithmetic (same colour shift, same affine_sample_px body) -> bit-identical to the fp32 kernel on x / 255.
+__global__ __launch_bounds__(256) void warp_new_frame_u8_kernel(const unsigned char* __restrict__ x, const WarpParams* __restrict__ wp,
+                                                                int B, int T, int H, int W, float* __restrict__ out) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long hw = (long)H * W;
+    if (idx >= (long)B * 3 * hw) return;
+    const int b = (int)(idx / (3 * hw));
+    const long r = idx - (long)b * 3 * hw;
+    const int c = (int)(r / hw);
+    const int pix = (int)(r - (long)c * hw);
+    const WarpParams& w = wp[b];
+    const unsigned char* src = x + ((long)b * T + w.j1) * hw * 3 + c;
+    float v;
+    if (w.mode == 2) {
+        const float m = (w.chan == 0 || w.chan - 1 == c) ? w.shift : 0.f;
+        v = fminf(fmaxf(u8_unit(src[3 * pix]) + m, 0.f), 1.f);
+    } else if (w.mode == 3) {
+        v = affine_sample_px([src](int i) { return u8_unit(src[3 * i]); }, H, W, w.th, pix / W, pix % W);
+    } else {
+        v = u8_unit(src[3 * pix]);
+    }
+    out[idx] = v;
+}
+
+// ---- a dataset's tokens resident in HBM: table [F, n] uint16, frame_index [rows] int64 -> out [rows, n] int64.  A row outside
+// [0, F) reads row 0 and is counted (faults[2], mmvid_device_faults).  VEC: n % 4 == 0 and the table 8-byte aligned -- a thread
+// moves 4 tokens: one 8-byte load, two 16-byte stores.
+template <bool VEC>
+__global__ __launch_bounds__(256) void token_rows_gather_kernel(const unsigned short* __restrict__ table, long F,
+                                                                const long long* __restrict__ frame_index, long rows, int n,
+                                                                long long* __restrict__ out, unsigned long long* __restrict__ faults) {
+    const int per = VEC ? (n >> 2) : n;  // threads per row
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= rows * per) return;
+    const long row = idx / per;
+    const int p = (int)(idx - row * per);
+    long long f = frame_index[row];
+    if (f < 0 || f >= F) {  // never fault; counted once per bad row
+        if (p == 0 && faults) atomicAdd(&faults[2], 1ull);
+        f = 0;
+    }
+    if (VEC) {
+        const uint2 w = *reinterpret_cast<const uint2*>(table + f * n + 4 * p);
+        longlong2* dst = reinterpret_cast<longlong2*>(out + row * n + 4 * p);
+        longlong2 lo, hi;
+        lo.x = (long long)(w.x & 0xffffu), lo.y = (long long)(w.x >> 16);
+        hi.x = (long long)(w.y & 0xffffu), hi.y = (long long)(w.y >> 16);
+        dst[0] = lo, dst[1] = hi;
+    } else {
+        out[row * n + p] = (long long)table[f * n + p];
+    }
+}
+
 // tokens of the VID negative from the target's tokens [B, T*n] and the new frames' tokens [B, n]
 __global__ __launch_bounds__(256) void warp_tokens_kernel(const long long* __restrict__ tok, const long long* __restrict__ extra,
                                                           const WarpParams* __restrict__ wp, int B, int T, int n,
@@ -475,6 +570,61 @@ extern "C" int mmvid_vid_warp_tokens(const int64_t* target_tok, const int64_t* n
     hipLaunchKernelGGL(warp_tokens_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const long long*)target_tok,
                        (const long long*)new_frame_tok, (const WarpParams*)params, B, T, n, (long long*)out);
     MMVID_LAUNCH_CHECK("vid_warp_tokens");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_frames_u8_to_f32(const uint8_t* frames_u8, int N, int H, int W, float* out, void* stream) {
+    MMVID_REQUIRE(frames_u8 && out && N >= 0 && H > 0 && W > 0, "frames_u8_to_f32: bad arguments");
+    if (N == 0) return MMVID_OK;
+    const long hw = (long)H * W;
+    if (hw % 4 == 0 && ((uintptr_t)frames_u8 & 3) == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(frames_u8_to_f32_kernel<true>, dim3(cdiv((long)N * (hw / 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                           frames_u8, (long)N, hw, out);
+    else
+        hipLaunchKernelGGL(frames_u8_to_f32_kernel<false>, dim3(cdiv((long)N * hw, 256)), dim3(256), 0, (hipStream_t)stream,
+                           frames_u8, (long)N, hw, out);
+    MMVID_LAUNCH_CHECK("frames_u8_to_f32");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_vid_warp_new_frames_u8(uint64_t seed, const float* step_dev, const uint8_t* x_u8, int B, int T, int H, int W,
+                                            const float* strategy_prob, void* params_scratch, int draw_params, float* new_frames,
+                                            void* stream) {
+    MMVID_REQUIRE(x_u8 && strategy_prob && params_scratch && new_frames, "vid_warp_new_frames_u8: null pointer");
+    MMVID_REQUIRE(B > 0 && T > 0 && T <= 32 && H > 0 && W > 0, "vid_warp_new_frames_u8: B=%d T=%d (T <= 32)", B, T);
+    hipStream_t s = (hipStream_t)stream;
+    if (draw_params)
+        hipLaunchKernelGGL(warp_params_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, seed, step_dev, B, T, strategy_prob[0],
+                           strategy_prob[1], strategy_prob[2], (WarpParams*)params_scratch);
+    const long total = (long)B * 3 * H * W;
+    hipLaunchKernelGGL(warp_new_frame_u8_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, x_u8, (const WarpParams*)params_scratch, B, T,
+                       H, W, new_frames);
+    MMVID_LAUNCH_CHECK("vid_warp_new_frames_u8");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_vid_warp_draw(uint64_t seed, const float* step_dev, int B, int T, const float* strategy_prob,
+                                   void* params_scratch, void* stream) {
+    MMVID_REQUIRE(strategy_prob && params_scratch && B > 0 && T > 0 && T <= 32, "vid_warp_draw: bad arguments");
+    hipLaunchKernelGGL(warp_params_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, seed, step_dev, B, T, strategy_prob[0],
+                       strategy_prob[1], strategy_prob[2], (WarpParams*)params_scratch);
+    MMVID_LAUNCH_CHECK("vid_warp_draw");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_token_rows_gather(const uint16_t* table, int64_t table_rows, const int64_t* frame_index, int64_t rows, int n,
+                                       int64_t* out, void* stream) {
+    MMVID_REQUIRE(table && frame_index && out && table_rows > 0 && rows >= 0 && n > 0, "token_rows_gather: bad arguments");
+    if (rows == 0) return MMVID_OK;
+    unsigned long long* faults = mmvid_fault_counters_dev();
+    MMVID_REQUIRE(faults, "token_rows_gather: the device fault counters are not reachable");
+    if (n % 4 == 0 && ((uintptr_t)table & 7) == 0 && ((uintptr_t)out & 15) == 0)
+        hipLaunchKernelGGL(token_rows_gather_kernel<true>, dim3(cdiv((long)rows * (n / 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                           table, (long)table_rows, (const long long*)frame_index, (long)rows, n, (long long*)out, faults);
+    else
+        hipLaunchKernelGGL(token_rows_gather_kernel<false>, dim3(cdiv((long)rows * n, 256)), dim3(256), 0, (hipStream_t)stream, table,
+                           (long)table_rows, (const long long*)frame_index, (long)rows, n, (long long*)out, faults);
+    MMVID_LAUNCH_CHECK("token_rows_gather");
     return MMVID_OK;
 }
 

@@ -402,12 +402,44 @@ class BERT(nn.Module):
             self._row_cache[key] = (rows, lab)
         return self._row_cache[key]
 
+    def _token_target_negative(self, target, target_frames, vid_strategy_prob):
+        """Tokens of the VID negative for a token-level target [B, T*n] int64.  The same draw as the pixel path (same variates,
+        same order, same call counter: equal seed and step -> equal decisions); of the pixels only the ONE new frame per sample is
+        made (vid_warp_new_frames[_u8]) and encoded, in the VQGAN's current `strict` mode.  Without `target_frames` only the two
+        strategies that move whole frames can be served."""
+        T = self.num_targets
+        B, device = target.shape[0], target.device
+        if target_frames is None:
+            if float(vid_strategy_prob[2]) + float(vid_strategy_prob[3]) > 0:
+                raise ValueError('token targets with vid=True: vid_strategy_prob gives the colour-shift / affine-warp strategies '
+                                 f'(entries 2 and 3: {list(vid_strategy_prob)[2:4]}) a non-zero probability, and those two make '
+                                 'new pixels. Pass target_frames (the frames of `target`, uint8 [B, T, H, W, 3] or fp32 '
+                                 '[B, T, 3, H, W]), or set both probabilities to 0.')
+            self.frontend.vid_warp_draw(B, T, device, vid_strategy_prob)
+            return self.frontend.vid_warp_tokens(target, target, T)  # (no sample reads the new-frame tokens in these modes)
+        s = self.vae.image_size
+        new = torch.empty(B, 3, s, s, device=device, dtype=torch.float32)
+        if target_frames.dtype == torch.uint8:
+            assert tuple(target_frames.shape) == (B, T, s, s, 3), \
+                f'target_frames: expected uint8 {(B, T, s, s, 3)}, got {tuple(target_frames.shape)}'
+            self.frontend.vid_warp_new_frames_u8(target_frames.contiguous(), vid_strategy_prob, new)
+        else:
+            assert tuple(target_frames.shape) == (B, T, 3, s, s), \
+                f'target_frames: expected fp32 {(B, T, 3, s, s)}, got {tuple(target_frames.shape)}'
+            self.frontend.vid_warp_new_frames(ops._chk(target_frames.contiguous().float(), torch.float32, 'target_frames'),
+                                              vid_strategy_prob, new)
+        return self.frontend.vid_warp_tokens(target, self.vae.get_codebook_indices(new), T)
+
     # ----------------------------------------------------------------------------------------- forward
     def forward(self, text, visual=None, target=None, mask=None, return_loss=False, rel=False, vid=False,
                 erase_visual=False, erase_visual_half=False, msm_strategy_prob=[0.7, 0.1, 0.1, 0.1],
                 msm_bernoulli_prob=[0.2, 0.5], rel_no_fully_masked=False,
                 vid_strategy_prob=[0.25, 0.25, 0.25, 0.25], negvc=False, visual_neg=None, text_neg=None, pc_prob=0,
-                vc_mode=None, face_mode=None, visual_aug_mode=None, _mask1=None, _target_warp=None, **kwargs):
+                vc_mode=None, face_mode=None, visual_aug_mode=None, _mask1=None, _target_warp=None, target_frames=None, **kwargs):
+        """`target` is the video [B, T, 3, H, W] in [0, 1], or its tokens [B, T*n] int64 (training from a token cache: the VQGAN is
+        frozen and the default transform is deterministic, so a frame's tokens never change).  With token targets and `vid`, the VID
+        negative still needs the pixels of ONE frame per sample when the colour-shift or affine strategy is drawn: pass
+        `target_frames`, the same frames as uint8 [B, T, H, W, 3] or fp32 [B, T, 3, H, W] (see _token_target_negative)."""
         device = text.device
         B = text.shape[0]
         text_rows = None
@@ -464,9 +496,12 @@ class BERT(nn.Module):
             toks = self.get_image_tokens(both)
             target, target_warp = toks[:B].contiguous(), toks[B:].contiguous()
         else:
+            token_target = torch.is_tensor(target) and target.dim() == 2 and not target.is_floating_point()
             target = self.get_image_tokens(target).contiguous()
-            if do_vid:
-                tw = _target_warp if _target_warp is not None else target  # token-level targets: nothing to warp
+            if do_vid and _target_warp is None and token_target:
+                target_warp = self._token_target_negative(target, target_frames, vid_strategy_prob)
+            elif do_vid:
+                tw = _target_warp if _target_warp is not None else target  # (a list of frames without an injected negative)
                 target_warp = self.get_image_tokens(tw.to(device)).contiguous()
         self.frontend.advance(device)
 

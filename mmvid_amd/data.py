@@ -131,14 +131,19 @@ def _natural_key(name):
     return [int(p) if p.isdigit() else p.lower() for p in _re.split(r'(\d+)', name)]
 
 
-def _load_frame(path, size):
-    """PIL image -> [3, size, size] float in [0, 1] (loader.py:414-417: Resize((size, size)) then to_tensor; bilinear)."""
+def _load_frame_u8(path, size):
+    """PIL image -> the resized frame as the decoder delivers it: numpy uint8 [size, size, 3] (what a token cache stores)."""
     import numpy as np
     from PIL import Image
     with Image.open(path) as im:
         im = im.convert('RGB').resize((size, size), Image.BILINEAR)
         arr = np.asarray(im, dtype=np.uint8)
-    return torch.from_numpy(arr.copy()).permute(2, 0, 1).float().div_(255.0)
+    return arr.copy()
+
+
+def _load_frame(path, size):
+    """PIL image -> [3, size, size] float in [0, 1] (loader.py:414-417: Resize((size, size)) then to_tensor; bilinear)."""
+    return torch.from_numpy(_load_frame_u8(path, size)).permute(2, 0, 1).float().div_(255.0)
 
 
 class TextVideoDataset(torch.utils.data.Dataset):

@@ -144,22 +144,42 @@ class Frontend:
             self._warp_scratch = torch.empty(nbytes, device=device, dtype=u8)
         return self._warp_scratch
 
-    def vid_warp_new_frames(self, x, strategy_prob, out):
+    def vid_warp_new_frames(self, x, strategy_prob, out, params=None):
         """Draw the warp parameters and write the ONE frame per sample whose pixels are new into out [B,C,H,W] (the rest
-        of the negative is frames the VQGAN has already tokenised: vid_warp_tokens)."""
+        of the negative is frames the VQGAN has already tokenised: vid_warp_tokens).  `params` (uint8, B * warp_params_bytes):
+        apply these instead of drawing (tests)."""
         ops._chk(x, f32, 'x')
         B, T, C, H, W = x.shape
         assert out.shape == (B, C, H, W) and out.is_contiguous() and out.dtype == f32
+        scratch, draw = (self._scratch(B, x.device), 1) if params is None else (ops._chk(params, u8, 'params'), 0)
         _lib.call('mmvid_vid_warp_new_frames', 0, _p(self._step(x.device)), _p(x), B, T, C, H, W,
-                  _farr(list(strategy_prob)), _p(self._scratch(B, x.device)), 1, _p(out), _stream())
+                  _farr(list(strategy_prob)), _p(scratch), draw, _p(out), _stream())
         return out
 
-    def vid_warp_tokens(self, target_tok, new_tok, T):
-        """target_tok [B, T*n], new_tok [B, n] -> tokens of the negative drawn by the last vid_warp_new_frames call."""
-        B, n = new_tok.shape
-        out = torch.empty_like(target_tok)
-        _lib.call('mmvid_vid_warp_tokens', _p(target_tok), _p(new_tok.contiguous()), _p(self._warp_scratch), B, T, n, _p(out),
+    def vid_warp_new_frames_u8(self, x_u8, strategy_prob, out, params=None):
+        """vid_warp_new_frames on x_u8 [B,T,H,W,3] uint8 (frames as an image decoder or a token cache delivers them): the same
+        draw, and out [B,3,H,W] bit-identical to vid_warp_new_frames on x_u8 / 255."""
+        ops._chk(x_u8, u8, 'x_u8')
+        B, T, H, W, C = x_u8.shape
+        assert C == 3 and out.shape == (B, 3, H, W) and out.is_contiguous() and out.dtype == f32
+        scratch, draw = (self._scratch(B, x_u8.device), 1) if params is None else (ops._chk(params, u8, 'params'), 0)
+        _lib.call('mmvid_vid_warp_new_frames_u8', 0, _p(self._step(x_u8.device)), _p(x_u8), B, T, H, W,
+                  _farr(list(strategy_prob)), _p(scratch), draw, _p(out), _stream())
+        return out
+
+    def vid_warp_draw(self, B, T, device, strategy_prob):
+        """Only the draw of vid_warp_new_frames (same stream, same call counter): enough for vid_warp_tokens when no strategy
+        that makes new pixels can be drawn (strategy_prob[2] == strategy_prob[3] == 0)."""
+        _lib.call('mmvid_vid_warp_draw', 0, _p(self._step(device)), B, T, _farr(list(strategy_prob)), _p(self._scratch(B, device)),
                   _stream())
+
+    def vid_warp_tokens(self, target_tok, new_tok, T, params=None):
+        """target_tok [B, T*n], new_tok [B, n] -> tokens of the negative drawn by the last vid_warp_new_frames[_u8] / vid_warp_draw
+        call (or of `params`).  new_tok is read only for the samples whose strategy made new pixels (colour shift, affine)."""
+        B, n = new_tok.shape[0], target_tok.shape[1] // T
+        out = torch.empty_like(target_tok)
+        _lib.call('mmvid_vid_warp_tokens', _p(target_tok), _p(new_tok.contiguous()), _p(self._warp_scratch if params is None else params),
+                  B, T, n, _p(out), _stream())
         return out
 
     def visual_color_jitter(self, visual, p=0.9, first_frame=1, want_params=False):

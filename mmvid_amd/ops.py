@@ -65,6 +65,28 @@ def gather_rows(table, idx, out_dtype=f32):
     return out
 
 
+def frames_u8_to_f32(frames_u8, out=None):
+    """[N, H, W, 3] uint8 (decoder layout) -> [N, 3, H, W] f32 = u8 / 255 (the division of ToTensor / data._load_frame, bit for bit)."""
+    _chk(frames_u8, torch.uint8, 'frames_u8')
+    N, H, W, C = frames_u8.shape
+    assert C == 3, f'frames_u8: expected [N, H, W, 3], got {tuple(frames_u8.shape)}'
+    if out is None:
+        out = torch.empty(N, 3, H, W, device=frames_u8.device, dtype=f32)
+    assert out.shape == (N, 3, H, W) and out.dtype == f32 and out.is_contiguous()
+    call('mmvid_frames_u8_to_f32', _p(frames_u8), N, H, W, _p(out), _stream())
+    return out
+
+
+def token_rows_gather(table, frame_index):
+    """table [F, n] uint16 on the device (TokenCache.to_device), frame_index [B, T] int64 -> target [B, T*n] int64.  An index
+    outside [0, F) reads row 0 and is counted (_lib.check_device_faults)."""
+    _chk(table, torch.uint16, 'table'), _chk(frame_index, i64, 'frame_index')
+    n = table.shape[1]
+    out = torch.empty(*frame_index.shape[:-1], frame_index.shape[-1] * n, device=table.device, dtype=i64)
+    call('mmvid_token_rows_gather', _p(table), table.shape[0], _p(frame_index), frame_index.numel(), n, _p(out), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- GEMM
 def gemm(A, B, *, a_kmajor=False, b_kmajor=False, bias=None, residual=None, dact_pre=None, save_pre=None, act=0,
          out_dtype=bf16, out=None, accumulate=False, splitk=1, alpha=1.0, colsum=None):
