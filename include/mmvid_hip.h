@@ -708,8 +708,62 @@ int mmvid_i3d_head(const void* x, int N, int To, int C, const float* w, const fl
 int mmvid_graph_stats(int64_t* counts);
 
 /* ---- run-time options; each is also read from an environment variable at first use.  "graphs" (MMVID_GRAPHS): 1 = library-level
- * graph replay (default 0).  Unknown names return MMVID_ERR_ARG. */
+ * graph replay (default 0).  "deterministic" (MMVID_DETERMINISTIC): 1 = the composite entries (mmvid_tower_backward) take every fp32
+ * sum in a fixed order through the *_det forms below and mmvid_layernorm_bwd* refuses its atomic branch (default 0: exactly the
+ * launches of the atomic forms).  Unknown names return MMVID_ERR_ARG.  mmvid_get_option reads the value in force. */
 int mmvid_set_option(const char* name, int value);
+int mmvid_get_option(const char* name, int* value);
+
+/* ---- deterministic forms of the training step's fp32 sums (torch.use_deterministic_algorithms is the familiar switch; the
+ * reference, train.py:298-325, leaves the order to torch's atomics).  No allocation, no host synchronisation: capturable.  Every
+ * workspace is the caller's, 16-byte aligned, its size from the matching *_workspace_bytes query; its contents are scratch.
+ * Below, "chain" means a sequential fp32 sum ((0.0f + a0) + a1) + ... in the stated order, and x (+)= t means x = x + t once.
+ *
+ * mmvid_colsum_bf16_det (bias gradients; dalle_bert.py:414-417 to_logits, clip_model.py:224-227 c_proj): block k covers rows
+ *   [256 k, 256 k + 256).  Per column: g_j = chain over the block's rows m with (m - 256 k) % 8 == j, ascending (j = 0..7);
+ *   block sum = chain (g_0 .. g_7); db[n] (+)= chain over the block sums, k ascending.
+ * mmvid_cross_entropy_fwd_det (dalle_bert.py:1040): lse as mmvid_cross_entropy_fwd.  term[row] = lse[row] - logits[row][target]
+ *   (the same fp32 expression) for a selected row, 0.0f otherwise; p_t = chain over term[t], term[t + 256], ... (t = 0..255);
+ *   loss_sum[0] (+)= chain (p_0 .. p_255).
+ * mmvid_assemble_sequence_bwd_det (the nn.Embedding gradients of dalle_bert.py:899-973): for every destination (table, id) that
+ *   occurs, its list = the rows r = b * L + l with seg[l] = table and ids[r] = id, ASCENDING in r (built on the device: integer
+ *   histogram, exclusive scan, rank of a row among the earlier rows with its key).  The list is cut into chunks of 64 consecutive
+ *   entries (the last one shorter); chunk sum = chain over the chunk's dx rows in list order; grad[table][id] (+)= chain over the
+ *   chunk sums in chunk order.  The order depends on (ids, seg, B, L) only.  Longest dependent chain: 64 + ceil(n / 64) adds for a
+ *   destination of n rows.  A row whose id is outside its table (or negative), or whose table has no gradient buffer, is skipped
+ *   as in mmvid_assemble_sequence_bwd (the forward counted it: mmvid_device_faults).  dpos as in mmvid_assemble_sequence_bwd (a
+ *   chain over b).  The rank pass compares every row with the rows before it: (B L)^2 / 2 integer compares (5.4e7 at B L = 10,422).
+ * mmvid_gemm_bf16_det: mmvid_gemm_bf16 with (a) out_colsum through a [ceil(M / 64)][N] slab: the epilogue stores, from its
+ *   registers, the sums of result rows [64 s, 64 s + 64) -- or of the block's whole row tile (128 / 256 rows) into the slab row of
+ *   its first 64 rows, the others staying 0 -- and out_colsum[n] (+)= chain over the slab rows, s ascending; (b) split-K through
+ *   [splitk][M][N] slabs: out_f32 (+)= chain over the slabs in split order.  RESTRICTION the atomic form does not have: with
+ *   splitk > 1 this form needs batch == 1 and ldc == N and returns MMVID_ERR_ARG otherwise (before anything is enqueued).  The sums inside a slab row are taken
+ *   in a fixed in-register order that is not part of this contract: the result is reproducible, not restated.
+ * mmvid_attention_bwd_bias_det: mmvid_attention_bwd_bias with dbias through per-wave partial rows [B][ceil(L / 128)][4][3E] (a wave
+ *   = 32 query rows for dq, 32 key rows for dk / dv; in-register order inside a wave as above): dbias[n] (+)= chain over the
+ *   partial rows in (batch, row tile, wave) order. */
+int64_t mmvid_colsum_bf16_det_workspace_bytes(int64_t M, int N);
+int mmvid_colsum_bf16_det(const void* dy, int64_t ld, int64_t M, int N, float* db, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+int64_t mmvid_cross_entropy_fwd_det_workspace_bytes(int64_t rows);
+int mmvid_cross_entropy_fwd_det(const float* logits, int64_t ldl, const int64_t* target, const uint8_t* select, int64_t rows,
+                                int V, float* lse, float* loss_sum, void* workspace, int64_t workspace_bytes, void* stream);
+/* (-1: sizes the 32-bit destination slots cannot hold) */
+int64_t mmvid_assemble_sequence_bwd_det_workspace_bytes(int64_t B, int L, int E, int ntables, const int64_t* table_rows);
+int mmvid_assemble_sequence_bwd_det(float* const* grad_tables, const int64_t* table_rows, int ntables, const int64_t* ids,
+                                    const int32_t* seg, const float* dx, int64_t B, int L, int E, float* dpos,
+                                    int accumulate_dpos, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t mmvid_gemm_bf16_det_workspace_bytes(int M, int N, int splitk, int with_colsum);
+int mmvid_gemm_bf16_det(int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int64_t lda, const void* B,
+                        int64_t ldb, int batch, int64_t strideA, int64_t strideB, int64_t strideC, int splitk,
+                        float alpha, const float* bias, const float* residual, int64_t ldr, const void* dact_pre,
+                        void* save_pre, int64_t ldp, int act, int accumulate, float* out_f32, void* out_bf16,
+                        int64_t ldc, float* out_colsum, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t mmvid_attention_bwd_bias_det_workspace_bytes(int B, int L, int E);
+int mmvid_attention_bwd_bias_det(const void* qkv, int64_t ld, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+                                 const float* lse2, float* delta, int B, int L, int H, int E, float scale, int mask_mode, int r0,
+                                 int c0, int r1, int c1, void* dqkv, int64_t ldg, float* dbias, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

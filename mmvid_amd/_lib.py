@@ -152,6 +152,12 @@ SIGNATURES = {
     'mmvid_prof_enable': [I],
     'mmvid_graph_stats': [P],
     'mmvid_set_option': [c_char_p, I],
+    'mmvid_get_option': [c_char_p, POINTER(I)],
+    'mmvid_colsum_bf16_det': [P, I64, I64, I, P, P, I64, P],
+    'mmvid_cross_entropy_fwd_det': [P, I64, P, P, I64, I, P, P, P, I64, P],
+    'mmvid_assemble_sequence_bwd_det': [POINTER(P), POINTER(I64), I, P, P, P, I64, I, I, P, I, P, I64, P],
+    'mmvid_gemm_bf16_det': [I, I, I, I, I, P, I64, P, I64, I, I64, I64, I64, I, F, P, P, I64, P, P, I64, I, I, P, P, I64, P, P, I64, P],
+    'mmvid_attention_bwd_bias_det': [P, I64, P, I64, P, I64, P, P, I, I, I, I, F, I, I, I, I, I, P, I64, P, P, I64, P],
     'mmvid_device_faults': [P, I],
     'mmvid_pos_table_fwd': [P, I, I, I, P, P],
     'mmvid_pos_table_bwd': [P, I, I, P, P],
@@ -179,7 +185,11 @@ SIGNATURES = {
 OTHER = {'mmvid_last_error': ([], c_char_p), 'mmvid_abi_version': ([], I), 'mmvid_device_count': ([], I),
          'mmvid_warp_params_bytes': ([], I), 'mmvid_gemm_dw_multi_fill': ([I, P, I], ctypes.c_double),
          'mmvid_tower_decode_persistent_supported': ([POINTER(TowerCfg), I], I),
-         'mmvid_tower_decode_persistent_workspace_bytes': ([I], I64)}
+         'mmvid_tower_decode_persistent_workspace_bytes': ([I], I64),
+         'mmvid_colsum_bf16_det_workspace_bytes': ([I64, I], I64), 'mmvid_cross_entropy_fwd_det_workspace_bytes': ([I64], I64),
+         'mmvid_assemble_sequence_bwd_det_workspace_bytes': ([I64, I, I, I, POINTER(I64)], I64),
+         'mmvid_gemm_bf16_det_workspace_bytes': ([I, I, I, I], I64),
+         'mmvid_attention_bwd_bias_det_workspace_bytes': ([I, I, I], I64)}
 
 class DwKind(ctypes.Structure):
     """mmvid_dw_kind_t (include/mmvid_hip.h)."""
@@ -224,21 +234,71 @@ def load():
         if have != ABI_VERSION:
             raise MMVIDError(f'{LIB_PATH} has ABI version {have}, this package needs {ABI_VERSION}: '
                              'rebuild with `python -m mmvid_amd.build --force`')
+        missing = []
+
+        def bind(name, args, res):
+            fn = getattr(lib, name, None)
+            if fn is None:
+                missing.append(name)
+            else:
+                fn.argtypes, fn.restype = args, res
+
         for name, args in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, I
+            bind(name, args, I)
         for name, (args, res) in OTHER.items():
-            fn = getattr(lib, name)
-            fn.argtypes, fn.restype = args, res
+            bind(name, args, res)
+        # An older build of the same ABI version given through MMVID_LIB (same-box A/Bs against a parent commit) lacks the entry points
+        # added since: it loads, and calling one of them raises.  The package's own library must have them all.
+        if missing and not os.environ.get('MMVID_LIB'):
+            raise MMVIDError(f'{LIB_PATH} lacks {missing[:4]}: rebuild with `python -m mmvid_amd.build --force`')
+        lib._mmvid_missing = frozenset(missing)
         _lib = lib
     return _lib
 
 
 def call(name, *args):
     lib = load()
+    if name in lib._mmvid_missing:
+        raise MMVIDError(f'{name} is not in {LIB_PATH} (an older build loaded through MMVID_LIB)')
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise MMVIDError(f'{name} failed (rc={rc}): {lib.mmvid_last_error().decode()}')
+
+
+# ---- deterministic mode: the library option "deterministic" is the one switch; the Python-side dispatch of ops.py reads it back,
+# so mmvid_set_option("deterministic", v) from any caller and MMVID_DETERMINISTIC switch the wrappers too
+def is_deterministic():
+    """True while the training step takes every fp32 sum in a fixed order.  Asked of the library every
+    time (one ctypes call, about a microsecond) rather than cached here, so that a direct mmvid_set_option -- tools/ab_multi.py, a C
+    caller in the same process -- switches the wrappers too and the two can never disagree."""
+    if 'mmvid_get_option' in load()._mmvid_missing:  # (a build from before the mode existed, through MMVID_LIB)
+        return False
+    v = c_int(0)
+    call('mmvid_get_option', b'deterministic', ctypes.byref(v))
+    return v.value != 0
+
+
+def set_deterministic(flag):
+    """Switch the deterministic mode of the library and of the Python wrappers.  Returns the previous value.  A GraphedStep keeps
+    the mode it was captured with and refuses to replay under the other one."""
+    prev = is_deterministic()
+    call('mmvid_set_option', b'deterministic', int(bool(flag)))
+    return prev
+
+
+class deterministic:
+    """`with mmvid_amd.deterministic():` (or `deterministic(False)`) -- the mode inside the block, the previous one after it."""
+
+    def __init__(self, flag=True):
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        self.prev = set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
 
 
 FAULT_NAMES = ('embedding id outside its table', 'cross-entropy target outside [0, V)', 'token-table row outside its table', 'reserved')

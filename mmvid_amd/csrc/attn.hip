@@ -267,6 +267,8 @@ __device__ __forceinline__ void store_row64(bf16_t* row_ptr, const f32x16 (&acc)
 // of the in-projection is the column sum of dqkv, and each backward kernel holds its rows of dq / dk / dv in registers right
 // before storing them (the separate colsum pass over dqkv was 13 us per layer).  A halving exchange: after step s a lane keeps
 // half of its remaining columns, summed with its partner's; 31 cross-lane moves for 32 columns, then one atomic per lane.
+// DET: dst is the wave's own row of a partial slab and the sums are stored (mmvid_attention_bwd_bias_det).
+template <bool DET>
 __device__ __forceinline__ void colsum_rows64(const f32x16 (&acc)[2], float scale, bool live, float* dst, int lane) {
     float cs[32];
 #pragma unroll
@@ -285,7 +287,16 @@ __device__ __forceinline__ void colsum_rows64(const f32x16 (&acc)[2], float scal
         }
     }
     const int c = lane & 31, h = lane >> 5;  // lane l of half h ends with column index c = l: d = 32 dt + 8 g4 + 4 h + e
-    unsafeAtomicAdd(dst + 32 * (c >> 4) + 8 * ((c >> 2) & 3) + 4 * h + (c & 3), cs[0]);
+    if (DET)
+        dst[32 * (c >> 4) + 8 * ((c >> 2) & 3) + 4 * h + (c & 3)] = cs[0];
+    else
+        unsafeAtomicAdd(dst + 32 * (c >> 4) + 8 * ((c >> 2) & 3) + 4 * h + (c & 3), cs[0]);
+}
+// DET: the slab row of a wave = ((b * row tiles + rt) * 4 + wave), 3E floats each; zeroed by the host, so a wave that stores nothing
+// (beyond L) contributes 0
+__device__ __forceinline__ float* dbias_slab_row(float* dbias, int b, int rt, int wave, int L, int E) {
+    const int nrt = (L + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+    return dbias + ((long)(b * nrt + rt) * 4 + wave) * 3 * E;
 }
 
 // Block coordinates: (row tile, head, batch) of a dispatch id; blocks of one (batch, head) are consecutive AND on one XCD: they share
@@ -488,6 +499,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const bf16_t* __restri
 }
 
 // ------------------------------------------------------------------------------------------ dQ
+template <bool DET>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, long ld, const bf16_t* __restrict__ O, long ldo,
                                                               const bf16_t* __restrict__ dO, long lddo, const float* __restrict__ lse2,
                                                               float* __restrict__ delta, int L, int H, int E, FastDiv nrt_d, FastDiv h_d,
@@ -637,7 +649,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const bf16_t* __res
     }
     mfma_settle(dq[0]), mfma_settle(dq[1]);
     if (q < L) store_row64(dqkv + ((long)b * L + q) * ldg + hd * 64, dq, scale, h);
-    if (dbias) colsum_rows64(dq, scale, q < L, dbias + hd * 64, lane);
+    if (dbias) colsum_rows64<DET>(dq, scale, q < L, (DET ? dbias_slab_row(dbias, b, qt, wave, L, E) : dbias) + hd * 64, lane);
 }
 
 // ------------------------------------------------------------------------------------------ dK, dV
@@ -660,6 +672,7 @@ __device__ __forceinline__ f32x16 row_consts(const float* st, int h) {
 // constants: -lse2 / scale_log2 and -delta are the INITIAL ACCUMULATORS of the S and dP chains (S' = S - lse2 / scale_log2, dP' = dP -
 // delta: P = exp2(scale_log2 S'), dS = P dP' -- no row-constant registers beside the accumulators, no subtraction), and the Q^T
 // fragments are requested only once P and dS are packed.
+template <bool DET>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, long ld, const bf16_t* __restrict__ dO, long lddo,
                                                                const float* __restrict__ lse2, const float* __restrict__ delta, int L, int H,
                                                                int E, FastDiv nrt_d, FastDiv h_d, float scale, float scale_log2,
@@ -798,8 +811,9 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_kernel(const bf16_t* __re
         store_row64(kp + E, dv, 1.0f, h_e);
     }
     if (dbias) {
-        colsum_rows64(dk, scale, key_e < L, dbias + E + hd * 64, lane_e);
-        colsum_rows64(dv, 1.0f, key_e < L, dbias + 2 * E + hd * 64, lane_e);
+        float* db = DET ? dbias_slab_row(dbias, b, kt, wave, L, E) : dbias;
+        colsum_rows64<DET>(dk, scale, key_e < L, db + E + hd * 64, lane_e);
+        colsum_rows64<DET>(dv, 1.0f, key_e < L, db + 2 * E + hd * 64, lane_e);
     }
 }
 
@@ -859,10 +873,10 @@ extern "C" int mmvid_attention_bwd(const void* qkv, int64_t ld, const void* O, i
                                     nullptr, stream);
 }
 
-extern "C" int mmvid_attention_bwd_bias(const void* qkv, int64_t ld, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+static int attention_bwd_impl(const void* qkv, int64_t ld, const void* O, int64_t ldo, const void* dO, int64_t lddo,
                                         const float* lse2, float* delta, int B, int L, int H, int E, float scale,
                                         int mask_mode, int r0, int c0, int r1, int c1, void* dqkv, int64_t ldg,
-                                        float* dbias, void* stream) {
+                                        float* dbias, float* det_slab, void* stream) {
     MMVID_REQUIRE(qkv && O && dO && lse2 && delta && dqkv, "attention_bwd: null pointer");
     ATTN_COMMON_CHECKS("attention_bwd");
     MMVID_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && ldg % 8 == 0 && ((uintptr_t)dqkv & 15) == 0,
@@ -875,10 +889,48 @@ extern "C" int mmvid_attention_bwd_bias(const void* qkv, int64_t ld, const void*
     MmvidProfScope prof(PROF_ATTN_BWD, 10.0 * B * H * (double)L * L * 64, s);  // 5 GEMM-equivalents (recompute counted once)
     const int nrt = cdiv(L, ROWS_PER_BLOCK), nblocks = nrt * H * B;
     const FastDiv nrt_d = make_fastdiv(nrt), h_d = make_fastdiv(H);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)O, (long)ldo,
+    if (dbias && det_slab) {  // per-wave partial rows (plain stores) + a fixed-order reduce instead of atomics
+        const int nslab = B * nrt * 4;
+        if (hipMemsetAsync(det_slab, 0, (size_t)nslab * 3 * E * 4, s) != hipSuccess) {
+            mmvid_set_error("attention_bwd_bias_det: memset failed");
+            return MMVID_ERR_HIP;
+        }
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)O, (long)ldo,
+                           (const bf16_t*)dO, (long)lddo, lse2, delta, L, H, E, nrt_d, h_d, scale, sl2, m, (bf16_t*)dqkv, (long)ldg, det_slab);
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)dO, (long)lddo,
+                           lse2, delta, L, H, E, nrt_d, h_d, scale, sl2, 1.0f / sl2, m, (bf16_t*)dqkv, (long)ldg, det_slab);
+        mmvid_slab_reduce(det_slab, nslab, 3 * E, dbias, s);
+        MMVID_LAUNCH_CHECK("attention_bwd_bias_det");
+        return MMVID_OK;
+    }
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)O, (long)ldo,
                        (const bf16_t*)dO, (long)lddo, lse2, delta, L, H, E, nrt_d, h_d, scale, sl2, m, (bf16_t*)dqkv, (long)ldg, dbias);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)dO, (long)lddo, lse2,
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, dim3(nblocks), dim3(256), 0, s, (const bf16_t*)qkv, (long)ld, (const bf16_t*)dO, (long)lddo, lse2,
                        delta, L, H, E, nrt_d, h_d, scale, sl2, 1.0f / sl2, m, (bf16_t*)dqkv, (long)ldg, dbias);
     MMVID_LAUNCH_CHECK("attention_bwd");
     return MMVID_OK;
+}
+
+extern "C" int mmvid_attention_bwd_bias(const void* qkv, int64_t ld, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+                                        const float* lse2, float* delta, int B, int L, int H, int E, float scale,
+                                        int mask_mode, int r0, int c0, int r1, int c1, void* dqkv, int64_t ldg,
+                                        float* dbias, void* stream) {
+    return attention_bwd_impl(qkv, ld, O, ldo, dO, lddo, lse2, delta, B, L, H, E, scale, mask_mode, r0, c0, r1, c1, dqkv, ldg, dbias,
+                              nullptr, stream);
+}
+
+extern "C" int64_t mmvid_attention_bwd_bias_det_workspace_bytes(int B, int L, int E) {
+    return (int64_t)B * cdiv(L > 0 ? L : 1, ROWS_PER_BLOCK) * 4 * 3 * E * 4;
+}
+
+extern "C" int mmvid_attention_bwd_bias_det(const void* qkv, int64_t ld, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+                                            const float* lse2, float* delta, int B, int L, int H, int E, float scale,
+                                            int mask_mode, int r0, int c0, int r1, int c1, void* dqkv, int64_t ldg,
+                                            float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (dbias)
+        MMVID_REQUIRE(workspace && B > 0 && L > 0 && workspace_bytes >= mmvid_attention_bwd_bias_det_workspace_bytes(B, L, E),
+                      "attention_bwd_bias_det: workspace of %lld bytes needed (mmvid_attention_bwd_bias_det_workspace_bytes)",
+                      (long long)mmvid_attention_bwd_bias_det_workspace_bytes(B, L, E));
+    return attention_bwd_impl(qkv, ld, O, ldo, dO, lddo, lse2, delta, B, L, H, E, scale, mask_mode, r0, c0, r1, c1, dqkv, ldg, dbias,
+                              (float*)workspace, stream);
 }

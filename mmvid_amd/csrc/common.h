@@ -112,7 +112,13 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // reductions, attention tail splits, packed softmax arithmetic, ...).  Each was decided by a whole-step measurement and the losing code
 // was deleted at the end of round 5; the logs under profiles/ (r01_ab_*, r03_ab_*, r04_gemm_*_experiment.log, r05_ab_whole_step_*) are
 // the record, and the comments next to the surviving code say what was measured against it.
-enum { MMVID_OPT_GRAPHS = 0, MMVID_OPT_COUNT = 1 };
+//   deterministic   MMVID_DETERMINISTIC   1 = every fp32 sum of the training step is taken in a fixed order (the `_det` entry points;
+//                           the composite entries -- mmvid_tower_backward -- switch to them; the LayerNorm backward refuses its
+//                           atomic branch); default 0: exactly the launches of the atomic forms
+enum { MMVID_OPT_GRAPHS = 0, MMVID_OPT_DETERMINISTIC = 1, MMVID_OPT_COUNT = 2 };
 int mmvid_option(int which);  // errors.hip
+// embed.hip: out[n] += sum_s slab[s][n] for s = 0 .. nslabs-1 in that order (one sequential fp32 chain per column, starting from
+// 0.0f; the total is then added to out[n]): the final combine of every per-block partial slab of the deterministic mode
+int mmvid_slab_reduce(const float* slab, int nslabs, int N, float* out, hipStream_t stream);
 // embed.hip: the device fault counters behind mmvid_device_faults() ([0] embedding ids, [1] cross-entropy targets, [2] token-table rows)
 unsigned long long* mmvid_fault_counters_dev();

@@ -131,6 +131,8 @@ __global__ __launch_bounds__(256) void batch_reduce_kernel(const float* __restri
 
 // ---- cross entropy over selected rows.  One wave per row, V % 4 == 0.
 // fwd: lse[row] saved; loss_sum += (lse - logit[target]) for selected rows (select[row] != 0).
+// DET: the selected row's term goes to loss_sum[row] (0 for a row that is not selected) instead of an atomic: ce_sum_det_kernel adds them.
+template <bool DET>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, long ldl,
                                                      const long long* __restrict__ target,
                                                      const unsigned char* __restrict__ select, long rows, int V,
@@ -139,7 +141,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     if (select && !select[row]) {
-        if (lane == 0) lse[row] = 0.f;
+        if (lane == 0) {
+            lse[row] = 0.f;
+            if (DET) loss_sum[row] = 0.f;
+        }
         return;
     }
     const float4* p = reinterpret_cast<const float4*>(logits + row * ldl);
@@ -163,7 +168,25 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
             atomicAdd(&g_faults[1], 1ull);
             t = 0;
         }
-        unsafeAtomicAdd(loss_sum, l - logits[row * ldl + t]);
+        if (DET)
+            loss_sum[row] = l - logits[row * ldl + t];
+        else
+            unsafeAtomicAdd(loss_sum, l - logits[row * ldl + t]);
+    }
+}
+
+// loss_sum[0] += the row terms in the documented order (include/mmvid_hip.h): thread t chains rows t, t + 256, ... from 0.0f, thread 0
+// then chains the 256 thread sums in thread order from 0.0f.  One block.
+__global__ __launch_bounds__(256) void ce_sum_det_kernel(const float* __restrict__ term, long rows, float* __restrict__ loss_sum) {
+    __shared__ float part[256];
+    float a = 0.f;
+    for (long r = threadIdx.x; r < rows; r += 256) a += term[r];
+    part[threadIdx.x] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int t = 0; t < 256; ++t) s += part[t];
+        loss_sum[0] += s;
     }
 }
 
@@ -200,6 +223,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 
 // db[n] += sum_m dY[m][n] (bf16 in, fp32 atomic out).  Thread = 8 columns (one 16-B load per row), block = 256
 // rows as 8 row-groups x 32 column-chunks reduced through LDS: one atomic per column per 256 rows.
+// DET: the block's sums go to row blockIdx.y of db = the [blocks][N] partial slab (plain stores) for mmvid_slab_reduce.
+template <bool DET>
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ dy, long ld, long M, int N,
                                                           float* __restrict__ db) {
     __shared__ float red[8][256];
@@ -227,7 +252,221 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restri
         float s = 0.f;
 #pragma unroll
         for (int r = 0; r < 8; ++r) s += red[r][col];
-        unsafeAtomicAdd(db + gn, s);
+        if (DET)
+            db[(long)blockIdx.y * N + gn] = s;
+        else
+            unsafeAtomicAdd(db + gn, s);
+    }
+}
+
+// out[n] += (((0 + slab[0][n]) + slab[1][n]) + ...).  A block owns 32 columns: its 256 threads stage 64 slab rows at a time in LDS
+// (coalesced 128-B row pieces, eight loads per thread in flight), then one thread per column chains them in row order.  (One thread
+// per column reading its own chain from memory was 13 us per call at 120 x 2304: nine blocks, each a chain of load latencies.)
+__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int nslabs, int N, float* __restrict__ out) {
+    __shared__ float tile[64][33];
+    const int c = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const int n = blockIdx.x * 32 + c;
+    float a = 0.f;
+    for (int s0 = 0; s0 < nslabs; s0 += 64) {
+        __syncthreads();
+#pragma unroll
+        for (int k = rl; k < 64; k += 8) tile[k][c] = (s0 + k < nslabs && n < N) ? slab[(long)(s0 + k) * N + n] : 0.f;
+        __syncthreads();
+        if (rl == 0) {  // all 64 rows (the ones past nslabs hold 0.0f: x + 0.0f = x): a fixed trip count lets the LDS reads pipeline
+#pragma unroll
+            for (int k = 0; k < 64; ++k) a += tile[k][c];
+        }
+    }
+    if (rl == 0 && n < N) out[n] += a;
+}
+
+// ---- deterministic embedding-table gradient (mmvid_assemble_sequence_bwd_det; the order is stated in include/mmvid_hip.h).
+// A destination is a table row: slot = (rows of the tables before it) + id, an int32.  Workspace (int32 unless noted):
+//   key[n]  rank[n]  list[n]  hist[nd + 1]  start[nd + 1]  cstart[nd + 1]  chunk_dest[maxc]  csum[maxc][E] fp32
+constexpr int DET_CH = 64;  // rows per first-level chunk
+struct DetTables {
+    float* t[MAX_TABLES];
+    long rows[MAX_TABLES];
+    int base[MAX_TABLES + 1];
+};
+struct DetWs {
+    int *key, *rank, *list, *hist, *start, *cstart, *chunk_dest;
+    float* csum;
+    long maxc, total;
+};
+inline long det_align(long b) { return (b + 255) & ~255l; }
+DetWs det_layout(char* base, long n, long nd, int E) {
+    DetWs w;
+    long off = 0;
+    auto take = [&](long bytes) {
+        char* p = base + off;
+        off += det_align(bytes);
+        return p;
+    };
+    w.maxc = (n < nd ? n : nd) + n / DET_CH + 1;  // every non-empty destination has at most one partly filled chunk
+    w.key = (int*)take(n * 4), w.rank = (int*)take(n * 4), w.list = (int*)take(n * 4);
+    w.hist = (int*)take((nd + 1) * 4), w.start = (int*)take((nd + 1) * 4), w.cstart = (int*)take((nd + 1) * 4);
+    w.chunk_dest = (int*)take(w.maxc * 4);
+    w.csum = (float*)take(w.maxc * (long)E * 4);
+    w.total = off;
+    return w;
+}
+// key[r] = destination slot of row r, or -1 (table without a gradient, id outside its table); hist[slot] = rows per destination
+// (integer atomics: exact)
+__global__ __launch_bounds__(256) void embdet_keys_kernel(DetTables tb, const long long* __restrict__ ids, const int* __restrict__ seg,
+                                                          long nrows, int L, int* __restrict__ key, int* __restrict__ hist) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    int k = -1;
+    if (r < nrows) {
+        const int s = seg[(int)(r % L)];
+        const long id = ids[r];
+        if (s >= 0 && s < MAX_TABLES && tb.t[s] && id >= 0 && id < tb.rows[s]) k = tb.base[s] + (int)id;
+        key[r] = k;
+    }
+    // one atomic per distinct key of the wave (the [MASK] destination takes half of all rows: one atomic per row serialised 5,000 of
+    // them on one address, 83 us)
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(k >= 0);
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int lk = __shfl(k, lead, 64);
+        const unsigned long long same = __ballot(k == lk);
+        if (lane == lead) atomicAdd(hist + lk, (int)__popcll(same));
+        todo &= ~same;
+    }
+}
+// rank[r] = number of rows r' < r with the same key: the position of r in its destination's ascending list.  Keys pass through
+// LDS in tiles of 256; a block only visits the tiles up to its own.
+__global__ __launch_bounds__(256) void embdet_rank_kernel(const int* __restrict__ key, long nrows, int* __restrict__ rank) {
+    __shared__ __attribute__((aligned(16))) int tile[256];
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    const int k = r < nrows ? key[r] : -1;
+    int cnt = 0;
+    for (int t = 0; t <= (int)blockIdx.x; ++t) {
+        const long j = (long)t * 256 + threadIdx.x;
+        __syncthreads();
+        tile[threadIdx.x] = j < nrows ? key[j] : -2;
+        __syncthreads();
+        if (k < 0) continue;  // (no barrier below this point of the iteration)
+        if (t < (int)blockIdx.x) {  // a whole tile of earlier rows: four keys per (broadcast) LDS read, fixed trip count
+#pragma unroll 16
+            for (int u = 0; u < 64; ++u) {
+                const int4 v = reinterpret_cast<const int4*>(tile)[u];
+                cnt += (v.x == k) + (v.y == k) + (v.z == k) + (v.w == k);
+            }
+        } else {  // the block's own tile: rows before r only
+            for (int u = 0; u < (int)threadIdx.x; ++u) cnt += tile[u] == k;
+        }
+    }
+    if (r < nrows) rank[r] = cnt;
+}
+// exclusive scans over the destinations, one block: start[d] = first list position of d, cstart[d] = first chunk of d;
+// start[nd] / cstart[nd] = totals.  Tiles of 8,192 counts pass through LDS (coalesced loads); a thread owns 8 consecutive ones.
+// (Each thread walking its own nd / 1024 strided counts from memory, twice, took 132 us at 50,497 destinations.)
+constexpr int SCAN_TILE = 8192;
+__global__ __launch_bounds__(1024) void embdet_scan_kernel(const int* __restrict__ hist, int nd, int* __restrict__ start,
+                                                           int* __restrict__ cstart) {
+    __shared__ int h[SCAN_TILE];
+    __shared__ int sr[1024], scn[1024], wr[16], wc[16], carry[2];
+    const int tid = threadIdx.x;
+    if (tid == 0) carry[0] = carry[1] = 0;
+    for (int t0 = 0; t0 < nd; t0 += SCAN_TILE) {
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = t0 + k * 1024 + tid;
+            h[k * 1024 + tid] = i < nd ? hist[i] : 0;
+        }
+        __syncthreads();
+        int ar = 0, ac = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ar += h[tid * 8 + k], ac += (h[tid * 8 + k] + DET_CH - 1) / DET_CH;
+        // inclusive scan of the 1,024 thread sums: inside each wave by shuffles, then the 16 wave totals through LDS
+        int ir = ar, ic = ac;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int vr = __shfl_up(ir, o, 64), vc = __shfl_up(ic, o, 64);
+            if ((tid & 63) >= o) ir += vr, ic += vc;
+        }
+        if ((tid & 63) == 63) wr[tid >> 6] = ir, wc[tid >> 6] = ic;
+        __syncthreads();
+        for (int w = 0; w < (tid >> 6); ++w) ir += wr[w], ic += wc[w];
+        sr[tid] = ir, scn[tid] = ic;
+        __syncthreads();
+        int br = carry[0] + sr[tid] - ar, bc = carry[1] + scn[tid] - ac;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int i = t0 + tid * 8 + k;
+            if (i < nd) start[i] = br, cstart[i] = bc;
+            br += h[tid * 8 + k], bc += (h[tid * 8 + k] + DET_CH - 1) / DET_CH;
+        }
+        __syncthreads();
+        if (tid == 1023) carry[0] += sr[1023], carry[1] += scn[1023];
+    }
+    __syncthreads();
+    if (tid == 0) start[nd] = carry[0], cstart[nd] = carry[1];
+}
+// list[start[key] + rank] = r (threads < nrows) and chunk_dest[cstart[d] + k] = d (threads < nd)
+__global__ __launch_bounds__(256) void embdet_place_kernel(const int* __restrict__ key, const int* __restrict__ rank, long nrows,
+                                                           const int* __restrict__ hist, const int* __restrict__ start,
+                                                           const int* __restrict__ cstart, int nd, int* __restrict__ list,
+                                                           int* __restrict__ chunk_dest) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < nrows) {
+        const int k = key[i];
+        if (k >= 0) list[start[k] + rank[i]] = (int)i;
+    }
+    if (i < nd) {
+        const int nc = (hist[i] + DET_CH - 1) / DET_CH, c0 = cstart[i];
+        for (int c = 0; c < nc; ++c) chunk_dest[c0 + c] = (int)i;
+    }
+}
+// level 1: block = chunk j: csum[j] = (((0 + dx[list[p]]) + dx[list[p + 1]]) + ...) over the chunk's list positions
+__global__ __launch_bounds__(256) void embdet_chunk_kernel(const int* __restrict__ list, const int* __restrict__ hist,
+                                                           const int* __restrict__ start, const int* __restrict__ cstart,
+                                                           const int* __restrict__ chunk_dest, int nd, const float* __restrict__ dx,
+                                                           int E, float* __restrict__ csum) {
+    const int j = blockIdx.x;
+    if (j >= cstart[nd]) return;
+    const int d = chunk_dest[j];
+    const int p0 = start[d] + (j - cstart[d]) * DET_CH;
+    const int p1 = min(p0 + DET_CH, start[d] + hist[d]);
+    for (int c = threadIdx.x; c < (E >> 2); c += 256) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int p = p0; p < p1; p += 8) {
+            float4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (p + u < p1) v[u] = *reinterpret_cast<const float4*>(dx + (long)list[p + u] * E + 4 * c);
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (p + u < p1) a.x += v[u].x, a.y += v[u].y, a.z += v[u].z, a.w += v[u].w;
+        }
+        *reinterpret_cast<float4*>(csum + (long)j * E + 4 * c) = a;
+    }
+}
+// level 2: the block of a destination's FIRST chunk chains the destination's chunk sums from 0.0f in chunk order and adds the
+// total to the table gradient row
+__global__ __launch_bounds__(256) void embdet_final_kernel(DetTables tb, const int* __restrict__ hist, const int* __restrict__ cstart,
+                                                           const int* __restrict__ chunk_dest, int nd, const float* __restrict__ csum,
+                                                           int E) {
+    const int j = blockIdx.x;
+    if (j >= cstart[nd]) return;
+    const int d = chunk_dest[j];
+    if (cstart[d] != j) return;
+    const int nc = (hist[d] + DET_CH - 1) / DET_CH;
+    int s = 0;
+    while (s + 1 < MAX_TABLES && d >= tb.base[s + 1]) ++s;
+    float* dst = tb.t[s] + (long)(d - tb.base[s]) * E;
+    for (int c = threadIdx.x; c < (E >> 2); c += 256) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int k = 0; k < nc; ++k) {
+            const float4 v = *reinterpret_cast<const float4*>(csum + (long)(j + k) * E + 4 * c);
+            a.x += v.x, a.y += v.y, a.z += v.z, a.w += v.w;
+        }
+        float4* o = reinterpret_cast<float4*>(dst + 4 * c);
+        const float4 g = *o;
+        *o = make_float4(g.x + a.x, g.y + a.y, g.z + a.z, g.w + a.w);
     }
 }
 
@@ -281,7 +520,7 @@ extern "C" int mmvid_cross_entropy_fwd(const float* logits, int64_t ldl, const i
     MMVID_REQUIRE(logits && target && lse && loss_sum, "cross_entropy_fwd: null pointer");
     MMVID_REQUIRE(V % 4 == 0 && ldl % 4 == 0, "cross_entropy_fwd: V and ldl must be multiples of 4");
     if (rows == 0) return MMVID_OK;
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, (long)ldl,
+    hipLaunchKernelGGL(ce_fwd_kernel<false>, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, (long)ldl,
                        (const long long*)target, select, (long)rows, V, lse, loss_sum);
     MMVID_LAUNCH_CHECK("cross_entropy_fwd");
     return MMVID_OK;
@@ -303,9 +542,103 @@ extern "C" int mmvid_colsum_bf16(const void* dy, int64_t ld, int64_t M, int N, f
     MMVID_REQUIRE(dy && db, "colsum_bf16: null pointer");
     MMVID_REQUIRE(N % 8 == 0 && ld % 8 == 0, "colsum_bf16: N and ld must be multiples of 8");
     if (M == 0) return MMVID_OK;
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3(cdiv(N, 256), cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(colsum_bf16_kernel<false>, dim3(cdiv(N, 256), cdiv(M, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)dy, (long)ld, (long)M, N, db);
     MMVID_LAUNCH_CHECK("colsum_bf16");
+    return MMVID_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- deterministic forms
+int mmvid_slab_reduce(const float* slab, int nslabs, int N, float* out, hipStream_t stream) {
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(N, 32)), dim3(256), 0, stream, slab, nslabs, N, out);
+    return MMVID_OK;
+}
+
+extern "C" int64_t mmvid_colsum_bf16_det_workspace_bytes(int64_t M, int N) { return (int64_t)cdiv(M > 0 ? M : 1, 256) * N * 4; }
+
+extern "C" int mmvid_colsum_bf16_det(const void* dy, int64_t ld, int64_t M, int N, float* db, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+    MMVID_REQUIRE(dy && db, "colsum_bf16_det: null pointer");
+    MMVID_REQUIRE(N % 8 == 0 && ld % 8 == 0, "colsum_bf16_det: N and ld must be multiples of 8");
+    if (M == 0) return MMVID_OK;
+    MMVID_REQUIRE(workspace && workspace_bytes >= mmvid_colsum_bf16_det_workspace_bytes(M, N),
+                  "colsum_bf16_det: workspace of %lld bytes needed (mmvid_colsum_bf16_det_workspace_bytes)",
+                  (long long)mmvid_colsum_bf16_det_workspace_bytes(M, N));
+    const int blocks = cdiv(M, 256);
+    hipLaunchKernelGGL(colsum_bf16_kernel<true>, dim3(cdiv(N, 256), blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
+                       (long)ld, (long)M, N, (float*)workspace);
+    mmvid_slab_reduce((const float*)workspace, blocks, N, db, (hipStream_t)stream);
+    MMVID_LAUNCH_CHECK("colsum_bf16_det");
+    return MMVID_OK;
+}
+
+extern "C" int64_t mmvid_cross_entropy_fwd_det_workspace_bytes(int64_t rows) { return (rows > 0 ? rows : 1) * 4; }
+
+extern "C" int mmvid_cross_entropy_fwd_det(const float* logits, int64_t ldl, const int64_t* target, const uint8_t* select,
+                                           int64_t rows, int V, float* lse, float* loss_sum, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    MMVID_REQUIRE(logits && target && lse && loss_sum, "cross_entropy_fwd_det: null pointer");
+    MMVID_REQUIRE(V % 4 == 0 && ldl % 4 == 0, "cross_entropy_fwd_det: V and ldl must be multiples of 4");
+    if (rows == 0) return MMVID_OK;
+    MMVID_REQUIRE(workspace && workspace_bytes >= rows * 4, "cross_entropy_fwd_det: workspace of %lld bytes needed", (long long)rows * 4);
+    hipLaunchKernelGGL(ce_fwd_kernel<true>, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, (long)ldl,
+                       (const long long*)target, select, (long)rows, V, lse, (float*)workspace);
+    hipLaunchKernelGGL(ce_sum_det_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, (long)rows, loss_sum);
+    MMVID_LAUNCH_CHECK("cross_entropy_fwd_det");
+    return MMVID_OK;
+}
+
+extern "C" int64_t mmvid_assemble_sequence_bwd_det_workspace_bytes(int64_t B, int L, int E, int ntables, const int64_t* table_rows) {
+    if (B < 0 || L <= 0 || E <= 0 || ntables < 1 || ntables > MAX_TABLES || !table_rows) return -1;
+    long nd = 0;
+    for (int i = 0; i < ntables; ++i) nd += table_rows[i] > 0 ? table_rows[i] : 0;
+    if (nd >= (1l << 31) - 1024 || B * L >= (1l << 31) - 1024) return -1;
+    return det_layout(nullptr, (long)B * L, nd, E).total;
+}
+
+extern "C" int mmvid_assemble_sequence_bwd_det(float* const* grad_tables, const int64_t* table_rows, int ntables,
+                                               const int64_t* ids, const int32_t* seg, const float* dx, int64_t B, int L, int E,
+                                               float* dpos, int accumulate_dpos, void* workspace, int64_t workspace_bytes,
+                                               void* stream) {
+    MMVID_REQUIRE(grad_tables && table_rows && ids && seg && dx, "assemble_sequence_bwd_det: null pointer");
+    MMVID_REQUIRE(ntables >= 1 && ntables <= MAX_TABLES && E % 4 == 0, "assemble_sequence_bwd_det: ntables=%d E=%d", ntables, E);
+    const long nrows = (long)B * L;
+    if (nrows == 0) return MMVID_OK;
+    const int64_t need = mmvid_assemble_sequence_bwd_det_workspace_bytes(B, L, E, ntables, table_rows);
+    MMVID_REQUIRE(need >= 0, "assemble_sequence_bwd_det: the rows of all tables, and B * L, must stay below 2^31");
+    MMVID_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0,
+                  "assemble_sequence_bwd_det: a 16-byte aligned workspace of %lld bytes is needed "
+                  "(mmvid_assemble_sequence_bwd_det_workspace_bytes)", (long long)need);
+    DetTables tb;
+    long nd = 0;
+    for (int i = 0; i < MAX_TABLES; ++i) {
+        tb.t[i] = i < ntables ? grad_tables[i] : nullptr;
+        tb.rows[i] = i < ntables ? table_rows[i] : 0;
+        tb.base[i] = (int)nd;
+        nd += tb.rows[i] > 0 ? tb.rows[i] : 0;
+    }
+    tb.base[MAX_TABLES] = (int)nd;
+    const DetWs w = det_layout((char*)workspace, nrows, nd, E);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(w.hist, 0, (size_t)(nd + 1) * 4, s) != hipSuccess) {
+        mmvid_set_error("assemble_sequence_bwd_det: memset failed");
+        return MMVID_ERR_HIP;
+    }
+    const int rb = cdiv(nrows, 256);
+    hipLaunchKernelGGL(embdet_keys_kernel, dim3(rb), dim3(256), 0, s, tb, (const long long*)ids, seg, nrows, L, w.key, w.hist);
+    hipLaunchKernelGGL(embdet_rank_kernel, dim3(rb), dim3(256), 0, s, w.key, nrows, w.rank);
+    hipLaunchKernelGGL(embdet_scan_kernel, dim3(1), dim3(1024), 0, s, w.hist, (int)nd, w.start, w.cstart);
+    hipLaunchKernelGGL(embdet_place_kernel, dim3(cdiv(nrows > nd ? nrows : nd, 256)), dim3(256), 0, s, w.key, w.rank, nrows, w.hist,
+                       w.start, w.cstart, (int)nd, w.list, w.chunk_dest);
+    hipLaunchKernelGGL(embdet_chunk_kernel, dim3((unsigned)w.maxc), dim3(256), 0, s, w.list, w.hist, w.start, w.cstart, w.chunk_dest,
+                       (int)nd, dx, E, w.csum);
+    hipLaunchKernelGGL(embdet_final_kernel, dim3((unsigned)w.maxc), dim3(256), 0, s, tb, w.hist, w.cstart, w.chunk_dest, (int)nd,
+                       w.csum, E);
+    if (dpos) {
+        const long LE = (long)L * E;
+        hipLaunchKernelGGL(batch_reduce_kernel, dim3(cdiv(LE / 4, 256)), dim3(256), 0, s, dx, (int)B, LE, dpos, accumulate_dpos);
+    }
+    MMVID_LAUNCH_CHECK("assemble_sequence_bwd_det");
     return MMVID_OK;
 }
 

@@ -33,7 +33,7 @@ struct Opt {
     int dflt, value;
     bool set;
 };
-Opt g_opts[MMVID_OPT_COUNT] = {{"graphs", "MMVID_GRAPHS", 0, 0, false}};
+Opt g_opts[MMVID_OPT_COUNT] = {{"graphs", "MMVID_GRAPHS", 0, 0, false}, {"deterministic", "MMVID_DETERMINISTIC", 0, 0, false}};
 }  // namespace
 
 int mmvid_option(int which) {
@@ -53,7 +53,19 @@ extern "C" int mmvid_set_option(const char* name, int value) {
             g_opts[i].value = value, g_opts[i].set = true;
             return MMVID_OK;
         }
-    mmvid_set_error("set_option: unknown option '%s' (graphs)", name);
+    mmvid_set_error("set_option: unknown option '%s' (graphs, deterministic)", name);
+    return MMVID_ERR_ARG;
+}
+
+// *value <- the option's current value (the environment variable is read here if nothing has set or read the option yet)
+extern "C" int mmvid_get_option(const char* name, int* value) {
+    MMVID_REQUIRE(name && value, "get_option: null pointer");
+    for (int i = 0; i < MMVID_OPT_COUNT; ++i)
+        if (strcmp(name, g_opts[i].name) == 0) {
+            *value = mmvid_option(i);
+            return MMVID_OK;
+        }
+    mmvid_set_error("get_option: unknown option '%s' (graphs, deterministic)", name);
     return MMVID_ERR_ARG;
 }
 

@@ -62,6 +62,7 @@ struct GemmParams {
     long ldc;
     float* partial;  // split-K workspace [splitk][M][N] (plain stores, reduced by splitk_reduce_kernel) or null
     float* colsum;   // [N] += column sums of the stored result (the bias gradient when the result is a dY), or null
+    int colsum_det;  // 1: `colsum` is a zeroed [cdiv(M, 64)][N] slab; the sums of rows [64 s, 64 s + 64) are STORED to row s (no atomics)
     int tiles_n, tiles_m;  // > 0: persistent blocks walk this tile grid (more tiles than CUs); 0: one block per tile
     int group_n;     // persistent blocks: tiles are walked column-GROUP-major (groups of group_n column tiles), see launch_shape
 };
@@ -190,7 +191,11 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, char* smem, f
             float a = 0.f;
 #pragma unroll
             for (int r = 0; r < RG; ++r) a += red[r * 128 + tid];
-            unsafeAtomicAdd(p.colsum + bn0 + tid, a);
+            if (p.colsum_det) {  // (a block's rows start at a multiple of 64: its sums take the slab row of its first 64 rows)
+                if (bm0 < p.M) p.colsum[(long)(bm0 >> 6) * p.N + bn0 + tid] = a;
+            } else {
+                unsafeAtomicAdd(p.colsum + bn0 + tid, a);
+            }
         }
     }
 }
@@ -285,7 +290,9 @@ __device__ __forceinline__ void pre_load(const GemmParams& p, const DirectEpi& d
 // column sums of a wave's 64 x 64 result: cs[c] (c = 16 j + 4 q + e, already summed over the lane's two rows) is reduced over the
 // 32 lanes of each half by a halving exchange -- 31 cross-lane moves instead of 160 -- after which lane l holds column l of its
 // half; one atomic per lane
-__device__ __forceinline__ void colsum_wave(float (&cs)[32], float* colsum, int bn0, int wn, int lane, int N) {
+__device__ __forceinline__ void colsum_wave(float (&cs)[32], const GemmParams& p, int bm0, int bn0, int wm, int wn, int lane) {
+    float* colsum = p.colsum;
+    const int N = p.N;
 #pragma unroll
     for (int s = 0; s < 5; ++s) {
         const int m = 1 << s;
@@ -299,7 +306,13 @@ __device__ __forceinline__ void colsum_wave(float (&cs)[32], float* colsum, int 
     }
     const int c = lane & 31, fh = lane >> 5;
     const int n = bn0 + wn * 64 + (c >> 4) * 32 + ((c >> 2) & 3) * 8 + 4 * fh + (c & 3);
-    if (n < N) unsafeAtomicAdd(colsum + n, cs[0]);
+    if (n >= N) return;
+    if (p.colsum_det) {  // the wave's 64 rows are slab row (bm0 + 64 wm) / 64
+        const int m0 = bm0 + wm * 64;
+        if (m0 < p.M) colsum[(long)(m0 >> 6) * N + n] = cs[0];
+    } else {
+        unsafeAtomicAdd(colsum + n, cs[0]);
+    }
 }
 // this lane's 32 bias values of a tile ([j][q] float4), read from the LDS copy BEFORE the next tile's LDS-DMA is requested (an LDS
 // read behind in-flight LDS-DMA makes hipcc drain vmcnt)
@@ -398,7 +411,7 @@ __device__ __forceinline__ void pending_fill_dact(const GemmParams& p, const Pre
             for (int k = 0; k < 2; ++k) pd.v[0][i][j][k] = widen_pair(out[2 * k], out[2 * k + 1]);
         }
     }
-    if (p.colsum) colsum_wave(cs, p.colsum, bn0, wn, lane, p.N);
+    if (p.colsum) colsum_wave(cs, p, bm0, bn0, wm, wn, lane);
 }
 
 // bias_lds: the whole bias vector [N] staged in LDS once per block (or null: no bias).  Returns nothing; d.nst stores were issued.
@@ -792,13 +805,14 @@ int launch(const GemmParams& p, int batch, hipStream_t stream) {
 
 }  // namespace
 
-// See include/mmvid_hip.h for the contract.
-extern "C" int mmvid_gemm_bf16(int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int64_t lda,
+// det_ws != null: the deterministic form (mmvid_gemm_bf16_det): column sums through a zeroed slab + mmvid_slab_reduce, split-K through
+// [splitk][M][N] slabs + splitk_reduce_kernel
+static int gemm_bf16_impl(int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int64_t lda,
                                const void* B, int64_t ldb, int batch, int64_t strideA, int64_t strideB,
                                int64_t strideC, int splitk, float alpha, const float* bias, const float* residual,
                                int64_t ldr, const void* dact_pre, void* save_pre, int64_t ldp, int act,
                                int accumulate, float* out_f32, void* out_bf16, int64_t ldc, float* out_colsum,
-                               void* stream) {
+                               float* det_ws, void* stream) {
     MMVID_REQUIRE(A && B && (out_f32 || out_bf16), "gemm_bf16: null pointer");
     MMVID_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, "gemm_bf16: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, batch);
     MMVID_REQUIRE(N % 8 == 0 && ldc % 4 == 0, "gemm_bf16: N (%d) must be a multiple of 8 and ldc of 4", N);
@@ -828,17 +842,66 @@ extern "C" int mmvid_gemm_bf16(int a_kmajor, int b_kmajor, int M, int N, int K, 
     p.dact_pre = (const bf16_t*)dact_pre, p.save_pre = (bf16_t*)save_pre, p.ldp = ldp;
     p.act = act, p.accumulate = accumulate, p.alpha = alpha;
     p.out_f32 = out_f32, p.out_bf16 = (bf16_t*)out_bf16, p.ldc = ldc;
-    p.partial = nullptr, p.colsum = out_colsum;
+    p.partial = nullptr, p.colsum = out_colsum, p.colsum_det = 0;
     p.tiles_n = p.tiles_m = 0, p.group_n = 0;
     hipStream_t s = (hipStream_t)stream;
+    const int nslab = cdiv(M, 64);
+    if (det_ws && splitk > 1) MMVID_REQUIRE(batch == 1 && ldc == N, "gemm_bf16_det: split-K needs batch == 1 and a dense result (ldc == N)");
+    if (det_ws && out_colsum) {
+        if (hipMemsetAsync(det_ws, 0, (size_t)nslab * N * 4, s) != hipSuccess) {
+            mmvid_set_error("gemm_bf16_det: memset failed");
+            return MMVID_ERR_HIP;
+        }
+        p.colsum = det_ws, p.colsum_det = 1;
+    }
+    if (det_ws && splitk > 1) p.partial = det_ws;
     if (!a_kmajor && !b_kmajor)
         launch<false, false>(p, batch, s);
     else if (!a_kmajor && b_kmajor)
         launch<false, true>(p, batch, s);
     else
         launch<true, true>(p, batch, s);
+    if (det_ws && out_colsum) mmvid_slab_reduce(det_ws, nslab, N, out_colsum, s);
+    if (det_ws && splitk > 1) {  // out_f32 += the slabs in slab order (the atomic form adds into out_f32 too)
+        const long mn = (long)M * N;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(mn / 4, 256)), dim3(256), 0, s, det_ws, splitk, mn, out_f32, 1);
+    }
     MMVID_LAUNCH_CHECK("gemm_bf16");
     return MMVID_OK;
+}
+
+// See include/mmvid_hip.h for the contract.
+extern "C" int mmvid_gemm_bf16(int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int64_t lda,
+                               const void* B, int64_t ldb, int batch, int64_t strideA, int64_t strideB,
+                               int64_t strideC, int splitk, float alpha, const float* bias, const float* residual,
+                               int64_t ldr, const void* dact_pre, void* save_pre, int64_t ldp, int act,
+                               int accumulate, float* out_f32, void* out_bf16, int64_t ldc, float* out_colsum,
+                               void* stream) {
+    return gemm_bf16_impl(a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, batch, strideA, strideB, strideC, splitk, alpha, bias, residual,
+                          ldr, dact_pre, save_pre, ldp, act, accumulate, out_f32, out_bf16, ldc, out_colsum, nullptr, stream);
+}
+
+extern "C" int64_t mmvid_gemm_bf16_det_workspace_bytes(int M, int N, int splitk, int with_colsum) {
+    if (splitk > 1) return (int64_t)splitk * M * N * 4;
+    return with_colsum ? (int64_t)cdiv(M, 64) * N * 4 : 0;
+}
+
+extern "C" int mmvid_gemm_bf16_det(int a_kmajor, int b_kmajor, int M, int N, int K, const void* A, int64_t lda,
+                                   const void* B, int64_t ldb, int batch, int64_t strideA, int64_t strideB,
+                                   int64_t strideC, int splitk, float alpha, const float* bias, const float* residual,
+                                   int64_t ldr, const void* dact_pre, void* save_pre, int64_t ldp, int act,
+                                   int accumulate, float* out_f32, void* out_bf16, int64_t ldc, float* out_colsum,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+    float* ws = nullptr;
+    if (M > 0 && N > 0 && (splitk > 1 || out_colsum)) {
+        const int64_t need = mmvid_gemm_bf16_det_workspace_bytes(M, N, splitk, out_colsum != nullptr);
+        MMVID_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0,
+                      "gemm_bf16_det: a 16-byte aligned workspace of %lld bytes is needed (mmvid_gemm_bf16_det_workspace_bytes)",
+                      (long long)need);
+        ws = (float*)workspace;
+    }
+    return gemm_bf16_impl(a_kmajor, b_kmajor, M, N, K, A, lda, B, ldb, batch, strideA, strideB, strideC, splitk, alpha, bias, residual,
+                          ldr, dact_pre, save_pre, ldp, act, accumulate, out_f32, out_bf16, ldc, out_colsum, ws, stream);
 }
 
 // Split factor for the dW GEMM: its output [N][K] has few tiles and the reduction (tokens) is long.  One wave of
@@ -869,7 +932,7 @@ extern "C" int mmvid_gemm_bf16_dw(int64_t M, int N, int K, const void* dY, int64
     p.act = 0, p.accumulate = accumulate, p.alpha = 1.0f;
     p.out_f32 = dW, p.out_bf16 = nullptr, p.ldc = K;
     p.partial = splitk > 1 ? workspace : nullptr;
-    p.colsum = nullptr;
+    p.colsum = nullptr, p.colsum_det = 0;
     p.tiles_n = p.tiles_m = 0, p.group_n = 0;
     hipStream_t s = (hipStream_t)stream;
     launch<true, true>(p, 1, s);
@@ -943,7 +1006,7 @@ extern "C" int mmvid_gemm_bf16_dw_multi(int64_t M, int nkinds, const mmvid_dw_ki
         p.bias = nullptr, p.residual = nullptr, p.ldr = 0, p.dact_pre = nullptr, p.save_pre = nullptr, p.ldp = 0;
         p.act = 0, p.accumulate = accumulate, p.alpha = 1.0f;
         p.out_f32 = nullptr, p.out_bf16 = nullptr, p.ldc = gt.kinds[0].N;
-        p.partial = nullptr, p.colsum = nullptr;
+        p.partial = nullptr, p.colsum = nullptr, p.colsum_det = 0;
         p.tiles_n = p.tiles_m = 0, p.group_n = 0;
         MmvidProfScope prof(PROF_GEMM_TN, flops, (hipStream_t)stream);
         hipLaunchKernelGGL(gemm_bf16_lw_grouped_kernel, dim3(tiles), dim3(512 + 64 * NLOAD), S::LDS_BYTES + BIAS_LDS_BYTES, (hipStream_t)stream, p, gt);

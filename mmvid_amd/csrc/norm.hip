@@ -725,6 +725,9 @@ static int layernorm_bwd_impl(const void* dy, int dy_is_bf16, int64_t lddy, cons
             partial = workspace;
         }
     }
+    MMVID_REQUIRE(partial || !any_red || !mmvid_option(MMVID_OPT_DETERMINISTIC),
+                  "layernorm_bwd: deterministic mode refuses the atomic dw / db / dx_colsum sums: pass a workspace of at least 64 * 3 * E "
+                  "floats (mmvid_layernorm_bwd_ws / mmvid_layernorm_bwd_ex / mmvid_layernorm_bwd_partial)");
     if (!partial) {
         // one-stage form (no workspace): the dw / db atomics scale with the grid -- measured on the whole step 2048 blocks: +0.6 ms,
         // 1024: +0.11 ms, 256: +0.25 ms against 512

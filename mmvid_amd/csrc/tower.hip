@@ -81,6 +81,17 @@ Scratch scratch_layout(const Dims& d) {
     return s;
 }
 
+// Deterministic mode (option "deterministic"): the backward's partial slabs -- the column sums of the d_pre GEMM, the attention
+// backward's per-wave in-projection bias sums, the partial rows of mmvid_colsum_bf16_det -- live in the `infer` region of the scratch
+// arena, which only a forward WITHOUT a saved arena touches.  The mode therefore needs no byte beyond what mmvid_tower_workspace
+// reports with the option off: a workspace sized before the option was set stays large enough.
+int64_t det_slab_bytes(const Dims& d) {
+    const int64_t a = mmvid_gemm_bf16_det_workspace_bytes((int)d.M, d.F, 1, 1);
+    const int64_t b = mmvid_attention_bwd_bias_det_workspace_bytes(d.B, d.L, d.E);
+    const int64_t c = mmvid_colsum_bf16_det_workspace_bytes(d.M, d.E);
+    return a > b ? (a > c ? a : c) : (b > c ? b : c);
+}
+
 #define TRY(call)                   \
     do {                            \
         int rc__ = (call);          \
@@ -104,7 +115,10 @@ int linear_fwd(int64_t M, int N, int K, const void* X, const void* W, const floa
 // dX = dY W (A = dY [M,N] row-major, B = W [N(red)][K(out)] k-major); out_colsum: [K] += column sums of dX, i.e. the
 // bias gradient of the Linear that produced this layer's input
 int linear_dx(int64_t M, int N, int K, const void* dY, const void* W, const void* dact_pre, float* out_f32,
-              void* out_bf16, void* st, float* out_colsum = nullptr) {
+              void* out_bf16, void* st, float* out_colsum = nullptr, void* det_ws = nullptr, int64_t det_bytes = 0) {
+    if (out_colsum && det_ws)
+        return mmvid_gemm_bf16_det(0, 1, (int)M, K, N, dY, N, W, K, 1, 0, 0, 0, 1, 1.0f, nullptr, nullptr, 0, dact_pre, nullptr, K,
+                                   0, 0, out_f32, out_bf16, K, out_colsum, det_ws, det_bytes, st);
     return mmvid_gemm_bf16(0, 1, (int)M, K, N, dY, N, W, K, 1, 0, 0, 0, 1, 1.0f, nullptr, nullptr, 0, dact_pre, nullptr, K,
                            0, 0, out_f32, out_bf16, K, out_colsum, st);
 }
@@ -203,7 +217,8 @@ extern "C" int mmvid_tower_backward(const mmvid_tower_cfg_t* cfg, const mmvid_to
                                     void* saved, void* scratch, void* stream) {
     TRY(check_cfg(cfg));
     MMVID_REQUIRE(layers && g && saved && scratch, "tower_backward: null pointer");
-    const uint64_t key = tower_key(3, cfg, layers, g, saved, scratch, nullptr, stream);
+    // (a library-level graph keeps the path it was captured with: the mode is part of its key)
+    const uint64_t key = tower_key(mmvid_option(MMVID_OPT_DETERMINISTIC) ? 5 : 3, cfg, layers, g, saved, scratch, nullptr, stream);
     return mmvid_run_cached(key, (hipStream_t)stream, [=](hipStream_t s) {
         return tower_backward_enqueue(cfg, layers, g, saved, scratch, (void*)s);
     });
@@ -226,6 +241,12 @@ static int tower_backward_enqueue(const mmvid_tower_cfg_t* cfg, const mmvid_towe
     const float scale = 0.125f;
     void* d_h = scr + sc.d_h;
     float* ws = (float*)(scr + sc.splitk_ws);
+    void* det_ws = nullptr;
+    const int64_t det_bytes = det_slab_bytes(d);
+    if (mmvid_option(MMVID_OPT_DETERMINISTIC)) {
+        MMVID_REQUIRE(det_bytes <= sc.total - sc.infer, "tower_backward: the deterministic slabs do not fit the scratch arena");
+        det_ws = scr + sc.infer;
+    }
     const int64_t ln_ws_floats = (int64_t)kLnBwdBlocks * 3 * d.E;
     std::vector<mmvid_ln_reduce_t> ln_items;
     int ln_blocks = 0;
@@ -236,10 +257,11 @@ static int tower_backward_enqueue(const mmvid_tower_cfg_t* cfg, const mmvid_towe
         void* g_pj = kp + kl.g_pj;  // bf16(g) in front of c_proj: the cast below (top layer of the call) or the layer above's LN1 backward
         if (i == d.layers - 1) {
             TRY(mmvid_cast_f32_to_bf16(g, g_pj, d.M * d.E, stream));
-            if (ly.g_pj_b) TRY(mmvid_colsum_bf16(g_pj, d.E, d.M, d.E, ly.g_pj_b, stream));
+            if (ly.g_pj_b && det_ws) TRY(mmvid_colsum_bf16_det(g_pj, d.E, d.M, d.E, ly.g_pj_b, det_ws, det_bytes, stream));
+            if (ly.g_pj_b && !det_ws) TRY(mmvid_colsum_bf16(g_pj, d.E, d.M, d.E, ly.g_pj_b, stream));
         }
         // d_pre = (g W_proj) * QuickGELU'(pre); its column sums are c_fc's bias gradient: taken in this epilogue (unrounded fp32 sums)
-        TRY(linear_dx(d.M, d.E, d.F, g_pj, ly.pj_w, sv + sl.pre, nullptr, kp + kl.d_pre, stream, ly.g_fc_b));
+        TRY(linear_dx(d.M, d.E, d.F, g_pj, ly.pj_w, sv + sl.pre, nullptr, kp + kl.d_pre, stream, ly.g_fc_b, det_ws, det_bytes));
         TRY(linear_dx(d.M, d.F, d.E, kp + kl.d_pre, ly.fc_w, nullptr, nullptr, d_h, stream));
         {
             mmvid_ln_reduce_t r = {(const float*)(kp + sl.k_ln2), ly.g_ln2_w, ly.g_ln2_b, ly.g_out_b};
@@ -251,9 +273,14 @@ static int tower_backward_enqueue(const mmvid_tower_cfg_t* cfg, const mmvid_towe
         }
         TRY(linear_dx(d.M, d.E, d.E, kp + kl.g_out, ly.out_w, nullptr, nullptr, scr + sc.d_o, stream));
         // (the in-projection's bias gradient -- column sums of dqkv -- comes out of the attention backward's registers)
-        TRY(mmvid_attention_bwd_bias(sv + sl.qkv, 3 * d.E, sv + sl.o, d.E, scr + sc.d_o, d.E, (const float*)(sv + sl.lse2),
-                                     (float*)(scr + sc.delta), d.B, d.L, d.H, d.E, scale, cfg->mask_mode, cfg->r0, cfg->c0,
-                                     cfg->r1, cfg->c1, kp + kl.dqkv, 3 * d.E, ly.g_in_b, stream));
+        if (det_ws)
+            TRY(mmvid_attention_bwd_bias_det(sv + sl.qkv, 3 * d.E, sv + sl.o, d.E, scr + sc.d_o, d.E, (const float*)(sv + sl.lse2),
+                                             (float*)(scr + sc.delta), d.B, d.L, d.H, d.E, scale, cfg->mask_mode, cfg->r0, cfg->c0,
+                                             cfg->r1, cfg->c1, kp + kl.dqkv, 3 * d.E, ly.g_in_b, det_ws, det_bytes, stream));
+        else
+            TRY(mmvid_attention_bwd_bias(sv + sl.qkv, 3 * d.E, sv + sl.o, d.E, scr + sc.d_o, d.E, (const float*)(sv + sl.lse2),
+                                         (float*)(scr + sc.delta), d.B, d.L, d.H, d.E, scale, cfg->mask_mode, cfg->r0, cfg->c0,
+                                         cfg->r1, cfg->c1, kp + kl.dqkv, 3 * d.E, ly.g_in_b, stream));
         TRY(linear_dx(d.M, 3 * d.E, d.E, kp + kl.dqkv, ly.in_w, nullptr, nullptr, d_h, stream));
         {
             mmvid_ln_reduce_t r = {(const float*)(kp + sl.k_ln1), ly.g_ln1_w, ly.g_ln1_b, i > 0 ? layers[i - 1].g_pj_b : nullptr};

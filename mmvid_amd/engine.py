@@ -524,6 +524,8 @@ class GraphedStep:
         self.trainer, self.fn = trainer, fn
         self.static = {k: v.clone() for k, v in example_inputs.items()}
         self.graph, self.capture_error = None, None
+        # a captured graph keeps the kernels of the mode it was captured with: recorded here, checked at every replay
+        self.deterministic = _lib.is_deterministic()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires (real training steps)
@@ -569,6 +571,10 @@ class GraphedStep:
         return loss.detach()
 
     def __call__(self, **inputs):
+        if _lib.is_deterministic() != self.deterministic:
+            raise RuntimeError(f'this GraphedStep was captured with deterministic={self.deterministic} and is called with '
+                               f'deterministic={_lib.is_deterministic()}: a replay would run the other mode\'s kernels; switch back '
+                               '(mmvid_amd.set_deterministic) or capture a new GraphedStep')
         for k, v in inputs.items():
             self.static[k].copy_(v, non_blocking=True)
         if self.graph is None:

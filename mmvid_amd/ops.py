@@ -23,6 +23,23 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+_DET_WS = {}  # (operator, device, bytes) -> uint8 workspace of a deterministic form, cached per shape
+
+
+def _det_ws(op, device, nbytes):
+    """The workspace of a `_det` entry point.  One buffer per (operator, size): launches are stream-ordered and every form
+    overwrites its workspace before reading it.  First use allocates -- during the warm-up steps that precede a capture
+    (engine.GraphedStep), never inside one."""
+    key = (op, str(device), int(nbytes))
+    ws = _DET_WS.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MMVIDError(f'{op}: the deterministic workspace ({nbytes} bytes) would be allocated inside a graph capture: '
+                                  'run the step once in deterministic mode before capturing it')
+        ws = _DET_WS[key] = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
+    return ws
+
+
 def _chk(t, dtype, name):
     if not t.is_cuda:
         raise _lib.MMVIDError(f'{name}: tensor is on {t.device}; the MMVID kernels run on an MI355X only (no CPU path)')
@@ -112,6 +129,13 @@ def gemm(A, B, *, a_kmajor=False, b_kmajor=False, bias=None, residual=None, dact
     for t, n in ((bias, 'bias'), (residual, 'residual')):
         if t is not None:
             _chk(t, f32, n)
+    if _lib.is_deterministic() and (colsum is not None or splitk > 1):  # the two fp32 atomic sums of this GEMM, in a fixed order
+        nb = _lib.load().mmvid_gemm_bf16_det_workspace_bytes(M, N, splitk, int(colsum is not None))
+        ws = _det_ws('gemm_bf16', A.device, nb)
+        call('mmvid_gemm_bf16_det', int(a_kmajor), int(b_kmajor), M, N, K, _p(A), A2.stride(0), _p(B), B2.stride(0), batch,
+             sA, sB, sC, splitk, float(alpha), _p(bias), _p(residual), N, _p(dact_pre), _p(save_pre), N, act,
+             int(accumulate), _p(out) if is32 else None, None if is32 else _p(out), N, _p(colsum), _p(ws), ws.numel(), _stream())
+        return out
     call('mmvid_gemm_bf16', int(a_kmajor), int(b_kmajor), M, N, K, _p(A), A2.stride(0), _p(B), B2.stride(0), batch,
          sA, sB, sC, splitk, float(alpha), _p(bias), _p(residual), N, _p(dact_pre), _p(save_pre), N, act,
          int(accumulate), _p(out) if is32 else None, None if is32 else _p(out), N, _p(colsum), _stream())
@@ -204,6 +228,8 @@ def layernorm_bwd(dy, x, mean, rstd, w, dx=None, add=False, dw=None, db=None, dx
     if dx is None:
         dx = torch.empty_like(x)
         add = False
+    if workspace is None and _lib.is_deterministic() and (dw is not None or db is not None or dx_colsum is not None):
+        workspace = _det_ws('layernorm_bwd', x.device, 512 * 3 * E * 4).view(f32)  # (the library refuses the atomic branch in this mode)
     call('mmvid_layernorm_bwd_ws', _p(dy), E, _p(x), E, _p(mean), _p(rstd), _p(w), rows, E, _p(dx), E, int(add), None,
          _p(dw), _p(db), _p(dx_colsum), _p(workspace), workspace.numel() if workspace is not None else 0, _stream())
     return dx
@@ -298,6 +324,11 @@ def attention_bwd(qkv, out, dout, lse2, B, L, H, mask=None, scale=0.125, dbias=N
     E = H * 64
     delta = torch.empty(B, H, L, device=qkv.device, dtype=f32)
     dqkv = torch.empty_like(qkv)
+    if dbias is not None and _lib.is_deterministic():
+        ws = _det_ws('attention_bwd_bias', qkv.device, _lib.load().mmvid_attention_bwd_bias_det_workspace_bytes(B, L, E))
+        call('mmvid_attention_bwd_bias_det', _p(qkv), 3 * E, _p(out), E, _p(dout), E, _p(lse2), _p(delta), B, L, H, E, float(scale),
+             *_mask_args(mask), _p(dqkv), 3 * E, _p(dbias), _p(ws), ws.numel(), _stream())
+        return dqkv
     call('mmvid_attention_bwd_bias', _p(qkv), 3 * E, _p(out), E, _p(dout), E, _p(lse2), _p(delta), B, L, H, E, float(scale),
          *_mask_args(mask), _p(dqkv), 3 * E, _p(dbias) if dbias is not None else None, _stream())
     return dqkv
@@ -330,6 +361,14 @@ def assemble_sequence_bwd(grad_tables, table_rows, ids, seg, dx, dpos=None, accu
     _chk(dx, f32, 'dx')
     tp, keep = _ptr_array(grad_tables)
     rows = (ctypes.c_int64 * len(grad_tables))(*table_rows)
+    if _lib.is_deterministic():  # inverted index + two-level fixed-order sums instead of the atomic scatter
+        nb = _lib.load().mmvid_assemble_sequence_bwd_det_workspace_bytes(B, L, E, len(grad_tables), rows)
+        if nb < 0:
+            raise _lib.MMVIDError('assemble_sequence_bwd: tables / batch too large for the deterministic form (2^31 destinations)')
+        ws = _det_ws('assemble_sequence_bwd', dx.device, nb)
+        call('mmvid_assemble_sequence_bwd_det', tp, rows, len(grad_tables), _p(ids), _p(seg), _p(dx), B, L, E, _p(dpos),
+             int(accumulate_dpos), _p(ws), ws.numel(), _stream())
+        return
     call('mmvid_assemble_sequence_bwd', tp, rows, len(grad_tables), _p(ids), _p(seg), _p(dx), B, L, E, _p(dpos),
          int(accumulate_dpos), _stream())
 
@@ -340,6 +379,11 @@ def cross_entropy_fwd(logits, target, select):
     rows, V = logits.shape
     lse = torch.empty(rows, device=logits.device, dtype=f32)
     loss = torch.zeros(1, device=logits.device, dtype=f32)
+    if _lib.is_deterministic():
+        ws = _det_ws('cross_entropy_fwd', logits.device, rows * 4)
+        call('mmvid_cross_entropy_fwd_det', _p(logits), V, _p(target), _p(select), rows, V, _p(lse), _p(loss), _p(ws), ws.numel(),
+             _stream())
+        return lse, loss
     call('mmvid_cross_entropy_fwd', _p(logits), V, _p(target), _p(select), rows, V, _p(lse), _p(loss), _stream())
     return lse, loss
 
@@ -354,6 +398,10 @@ def cross_entropy_bwd(logits, target, select, lse, gscale):
 
 def colsum_bf16(dy, db):
     M, N = dy.shape
+    if _lib.is_deterministic():
+        ws = _det_ws('colsum_bf16', dy.device, _lib.load().mmvid_colsum_bf16_det_workspace_bytes(M, N))
+        call('mmvid_colsum_bf16_det', _p(dy), N, M, N, _p(db), _p(ws), ws.numel(), _stream())
+        return
     call('mmvid_colsum_bf16', _p(dy), N, M, N, _p(db), _stream())
 
 

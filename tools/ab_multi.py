@@ -41,7 +41,7 @@ def main():
     fn = bench.loss_fn(model, 2)
     for _ in range(2):
         bench.eager_step(tr, fn, inputs)
-    steps = {}
+    steps, lib_opts = {}, {}
     for c in configs:
         ov = {} if c == 'base' else dict(kv.split('=') for kv in c.split(','))
         for k, v in DEFAULTS.items():
@@ -50,11 +50,16 @@ def main():
             if k not in DEFAULTS:
                 apply(model, k, v)
         steps[c] = GraphedStep(tr, fn, inputs, warmup=1)
+        lib_opts[c] = {k: v for k, v in ov.items() if not k.startswith('py:')}
+        for k in lib_opts[c]:  # library options default to 0
+            apply(model, k, 0)
     for k, v in DEFAULTS.items():
         apply(model, k, v)
     res = {c: [] for c in configs}
     for rep in range(8):
         for c in configs:
+            for k, v in lib_opts[c].items():  # (a graph keeps its kernels; a GraphedStep refuses a replay under another "deterministic")
+                apply(model, k, v)
             steps[c]()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -62,6 +67,8 @@ def main():
                 steps[c]()
             torch.cuda.synchronize()
             res[c].append((time.perf_counter() - t0) / 5 * 1e3)
+            for k in lib_opts[c]:
+                apply(model, k, 0)
     base = np.median(res[configs[0]])
     for c in configs:
         m = np.median(res[c])
