@@ -253,6 +253,11 @@ int mmvid_vid_warp_tokens(const int64_t* target_tok, const int64_t* new_frame_to
  * frames_u8 [N, H, W, 3] uint8, as image decoders deliver it -> out [N, 3, H, W] fp32 = float(u8) / 255.0f (a correctly rounded
  * division: the arithmetic of torchvision's ToTensor and of data._load_frame). */
 int mmvid_frames_u8_to_f32(const uint8_t* frames_u8, int N, int H, int W, float* out, void* stream);
+/* ---- the output side (mmvid_amd/long_video.py): utils/utils_html.py:157-186 quantisation on the device, replacing
+ * `tensor.cpu().clamp(0, 1) * 255 -> uint8 -> permute`: img [N,3,H,W] fp32 -> out [N,H,W,3] uint8,
+ * out = (uint8) trunc(min(max(x, 0), 1) * 255), one fp32 multiply, no fma; NaN -> 0.
+ * Needs (H * W) % 4 == 0, img 16-byte aligned and out 4-byte aligned (MMVID_ERR_ARG otherwise, nothing is launched). */
+int mmvid_frames_to_u8(const float* img, int64_t N, int H, int W, uint8_t* out, void* stream);
 /* mmvid_vid_warp_new_frames on x_u8 [B, T, H, W, 3] uint8: same WarpParams, same Philox stream and call counter, same
  * draw_params switch.  A pixel becomes u8 / 255 when it is loaded and the colour shift / affine bilinear sample run on those
  * values in the fp32 kernel's operation order: new_frames [B, 3, H, W] is bit-identical to the fp32 kernel on x = u8 / 255. */

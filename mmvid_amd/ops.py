@@ -94,6 +94,20 @@ def frames_u8_to_f32(frames_u8, out=None):
     return out
 
 
+def frames_to_u8(img, out=None):
+    """[N, 3, H, W] f32 (what vae.decode returns) -> [N, H, W, 3] uint8 = trunc(clamp(x, 0, 1) * 255): the quantisation of
+    data.save_image_tensor (utils_html.py:157-186) bit for bit, NaN -> 0.  H * W must be a multiple of 4."""
+    _chk(img, f32, 'img')
+    N, C, H, W = img.shape
+    assert C == 3, f'img: expected [N, 3, H, W], got {tuple(img.shape)}'
+    if out is None:
+        out = torch.empty(N, H, W, 3, device=img.device, dtype=torch.uint8)
+    _chk(out, torch.uint8, 'out')
+    assert out.shape == (N, H, W, 3)
+    call('mmvid_frames_to_u8', _p(img), N, H, W, _p(out), _stream())
+    return out
+
+
 def token_rows_gather(table, frame_index):
     """table [F, n] uint16 on the device (TokenCache.to_device), frame_index [B, T] int64 -> target [B, T*n] int64.  An index
     outside [0, F) reads row 0 and is counted (_lib.check_device_faults)."""

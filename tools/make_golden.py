@@ -9,7 +9,7 @@ layout), and the reference's outputs.  Run:
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [case ...]
 
 Cases: vq vqgan_tiny vqgan_full vqgan_full16 vqgan_full16_refinit tower tower12 bert_tiny bert_tiny_visual bert_negvc bert_negvc_visual bert_flm bert_flm_bottleneck artv_tiny mask_predict
-       frontend mask_predict_race clip_vit2 clip_vit12 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd
+       frontend mask_predict_race clip_vit2 clip_vit12 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd long_video
 """
 import json
 import os
@@ -1008,13 +1008,91 @@ def case_fvd_prd():
     save('fvd_prd_ref', meta=dict(n_hists=len(hists)), **arrs)
 
 
+LONG_VIDEO_CASES = [('long', 4, 3, 1), ('long', 4, 3, 2), ('long', 8, 4, 3), ('interp', 4, 3, 1), ('interp', 8, 2, 1), ('interp', 2, 3, 1),
+                    ('interp_real', 4, 2, 1), ('interp_real', 4, 3, 1), ('interp_real', 8, 2, 1), ('interp_real', 8, 3, 1),
+                    ('interp_real', 8, 4, 1), ('interp_real', 16, 3, 1)]  # (mode, num_targets, t_repeat, t_overlap)
+
+
+def case_long_video():
+    """utils/utils_train.py visualize_long (1221-1653) driven with a recording stand-in for `dalle_module`: every generated frame is
+    one token and one pixel holding a fresh integer id (call number * T + slot), preserved ids are placed as dalle_bert.py:558-580
+    places them, real frame f has id 900000 + f.  Per case: the (preserve, t_overlap, long_mode, output) of every generate_images
+    call and the final timeline of ids that visualize_long hands to get_codebook_emb.  Integers only."""
+    import pathlib
+    import tempfile
+    import types
+    for mod in ('imageio', 'dominate', 'dominate.tags', 'dominate.util'):  # utils/utils_train.py's driver-side imports
+        sys.modules.setdefault(mod, types.ModuleType(mod))
+    sys.modules['dominate'].document = lambda *a, **k: None
+    sys.modules['dominate.util'].raw = lambda *a, **k: None
+    import utils.utils_train as ut
+    MASK, NONE = -1, -2  # in the logged preserve rows: a [MASK] slot / no preserve argument at all
+
+    class Recorder:
+        def __init__(self, T):
+            self.num_targets = self.target_seq_len = T  # image_seq_len = 1
+            self.image_token_lut = {'[MASK]': MASK}
+            self.calls, self.timeline = [], None
+
+        def generate_images(self, text, *, preserve=None, t_overlap=1, long_mode='long', **kw):
+            T, k = self.num_targets, len(self.calls)
+            assert text.shape[0] == 1
+            ids = torch.arange(k * T, (k + 1) * T)
+            logged = torch.full((T, ), NONE)
+            if preserve is not None:
+                logged = preserve.reshape(T).clone()
+                if long_mode == 'long':
+                    if t_overlap:
+                        ids[:t_overlap] = logged[T - t_overlap:]
+                else:
+                    ids[::2] = logged[:T // 2]
+            self.calls.append((logged, int(t_overlap), long_mode, ids.clone()))
+            return ids.float().view(1, T, 1, 1, 1), [], ids.view(T, 1)
+
+        def recon_images(self, images, **kw):
+            return images
+
+        def get_image_tokens(self, image, reshape=True, which_vae='vae'):
+            assert reshape
+            return 900000 + image[:, :, 0, 0, 0].long()
+
+        def get_codebook_emb(self, images, which_vae='vae'):
+            self.timeline = images[0, :, 0, 0, 0].long().clone()
+            return torch.zeros(1), torch.zeros(1)
+
+    tokenizer = types.SimpleNamespace(decode=lambda toks: 'a caption')
+    cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda t, *a, **k: t
+    arrs, meta = {}, []
+    try:
+        with tempfile.TemporaryDirectory() as tmp:
+            for i, (mode, T, r, o) in enumerate(LONG_VIDEO_CASES):
+                rec = Recorder(T)
+                args = types.SimpleNamespace(fixed_language_model=None, n_sample=1, batch_size=1, num_targets=T, num_visuals=0, image_size=1,
+                                             log_sample_dir=pathlib.Path(tmp), use_cvae=None, pnag_dynamic=False, use_html=False, visual=False,
+                                             rand_visual=False, debug=False, long_mode=mode, t_overlap=o, t_repeat=r, mp_config=MP_CONFIG,
+                                             pc_mode=None, save_codebook=True, fullvc=False, text_seq_len=4)
+                frames = torch.arange(T, dtype=torch.float32).view(1, T, 1, 1, 1).expand(1, T, 1, 1, 1).clone()
+                batch = dict(description=['a caption'], text=torch.tensor([[5, 6, 0, 0]]), target=frames, visual=torch.zeros(1, 0, 1, 1, 1))
+                ut.visualize_long(args, rec, tokenizer, batch, which_iter='golden')
+                arrs[f'c{i}_preserve'] = torch.stack([c[0] for c in rec.calls])
+                arrs[f'c{i}_t_overlap'] = torch.tensor([c[1] for c in rec.calls])
+                arrs[f'c{i}_out'] = torch.stack([c[3] for c in rec.calls])
+                arrs[f'c{i}_timeline'] = rec.timeline
+                meta.append(dict(mode=mode, num_targets=T, t_repeat=r, t_overlap=o, long_mode=[c[2] for c in rec.calls]))
+                print(mode, T, r, o, 'calls', len(rec.calls), 'frames', rec.timeline.numel())
+    finally:
+        torch.Tensor.cuda = cuda
+    save('long_video_plan', meta=dict(mask=MASK, none=NONE, real_base=900000, cases=meta), **arrs)
+
+
 CASES = dict(vq=case_vq, vqgan_tiny=case_vqgan_tiny, vqgan_full=case_vqgan_full, vqgan_full16=case_vqgan_full16,
              vqgan_full16_refinit=case_vqgan_full16_refinit, tower=case_tower, tower12=case_tower12,
              bert_tiny=case_bert_tiny, bert_tiny_visual=case_bert_tiny_visual, bert_negvc=case_bert_negvc, bert_negvc_visual=case_bert_negvc_visual, bert_flm=case_bert_flm,
              bert_flm_bottleneck=case_bert_flm_bottleneck, artv_tiny=case_artv_tiny,
              mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race,
              clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12, roberta_tokenizer=case_roberta_tokenizer, roberta_tiny=case_roberta_tiny,
-             roberta_large24=case_roberta_large24, fvd_prd=case_fvd_prd)
+             roberta_large24=case_roberta_large24, fvd_prd=case_fvd_prd, long_video=case_long_video)
 
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
