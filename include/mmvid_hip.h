@@ -329,7 +329,15 @@ int mmvid_tower_backward(const mmvid_tower_cfg_t* cfg, const mmvid_tower_layer_t
  * every sampled token (SURVEY next-row N1).  kv_cache: [layers][B][Lmax][2E] bf16, a row = K then V of one position.
  * prefill = the causal forward over the prompt (cfg->L positions) that also fills the cache; decode = one new
  * position per sequence (x_in / x_out [B, E] fp32) at index *pos_dev (device scalar: the call can be captured and
- * replayed for every position) or `pos` when pos_dev is NULL.  Needs cfg->mask_mode == 1; scratch as for the forward. */
+ * replayed for every position) or `pos` when pos_dev is NULL.  Needs cfg->mask_mode == 1; scratch as for the forward.
+ * Contract of a decode step at position p (every form below; pinned bit for bit by tests/test_decode_exact_gpu.py):
+ *   - per layer it READS cache rows 0 .. p-1 of its cfg->B sequences and nothing else of the cache: rows >= p may hold anything
+ *     (NaN included), row p is never read -- the new position's K | V come from this step's own in-projection;
+ *   - it WRITES row p of every layer and sequence (K | V of the new position, rounded to bf16 once) and no other cache element;
+ *   - the new position attends n = p + 1 keys: rows 0 .. p-1 and itself; p = Lmax - 1 is the last valid step (all Lmax rows in use);
+ *   - with p >= Lmax the fused and persistent forms append nothing and attend the Lmax cached rows (never out of bounds; the result
+ *     is no position of the sequence); mmvid_tower_decode rejects a host-side `pos` >= Lmax;
+ *   - advance_pos: *pos_dev becomes p + 1, once per step, after every launch of the step has read it. */
 int mmvid_tower_prefill(const mmvid_tower_cfg_t* cfg, const mmvid_tower_layer_t* layers, const float* x_in,
                         float* x_out, void* kv_cache, int Lmax, void* scratch, void* stream);
 int mmvid_tower_decode(const mmvid_tower_cfg_t* cfg, const mmvid_tower_layer_t* layers, const float* x_in, float* x_out,
