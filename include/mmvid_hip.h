@@ -258,6 +258,14 @@ int mmvid_frames_u8_to_f32(const uint8_t* frames_u8, int N, int H, int W, float*
  * out = (uint8) trunc(min(max(x, 0), 1) * 255), one fp32 multiply, no fma; NaN -> 0.
  * Needs (H * W) % 4 == 0, img 16-byte aligned and out 4-byte aligned (MMVID_ERR_ARG otherwise, nothing is launched). */
 int mmvid_frames_to_u8(const float* img, int64_t N, int H, int W, uint8_t* out, void* stream);
+/* ... with the known pixels of a completed video (mmvid_amd/completion.py) pasted over their reconstruction:
+ * out = given[token of the pixel] ? real : q(img), q the quantisation of mmvid_frames_to_u8 (the same kernel body).
+ * img [N,3,H,W] fp32, real [N,H,W,3] uint8, given [N,h,w] uint8 (non-zero = known; the token of pixel (y, x) is
+ * (y / (H/h), x / (W/w))), out [N,H,W,3] uint8.  A NaN of img under a given token leaves real, elsewhere it gives 0.
+ * Needs H % h == 0, W % w == 0, (W / w) % 4 == 0 (the 4 pixels of a 16-byte load lie in one token), (H * W) % 4 == 0, img 16-byte
+ * aligned, real and out 4-byte aligned (MMVID_ERR_ARG otherwise, nothing is launched). */
+int mmvid_frames_paste_u8(const float* img, const uint8_t* real, const uint8_t* given, int64_t N, int H, int W, int h, int w,
+                          uint8_t* out, void* stream);
 /* mmvid_vid_warp_new_frames on x_u8 [B, T, H, W, 3] uint8: same WarpParams, same Philox stream and call counter, same
  * draw_params switch.  A pixel becomes u8 / 255 when it is loaded and the colour shift / affine bilinear sample run on those
  * values in the fp32 kernel's operation order: new_frames [B, 3, H, W] is bit-identical to the fp32 kernel on x = u8 / 255. */
@@ -468,6 +476,12 @@ int mmvid_sample_race_at(const float* logits, int64_t ld, const float* E, const 
  * stay.  Y [b, TS], E [b, Bm, TS], mask1 out [b, Bm, TS] (1 = keep). */
 int mmvid_mp_select_keep(const float* Y, const float* E, const uint8_t* preserve, int b, int Bm, int TS, int k,
                          uint8_t* mask1, void* stream);
+/* The same kernel with a mask and a keep count per video (video completion, mmvid_amd/completion.py): given [b, TS] uint8
+ * (non-zero = known, always stays), k_rows int32 [b] on the device.  Video i keeps the k_rows[i] valid positions with the smallest
+ * E / Y; the fallback is applied per video (k_rows[i] outside [1, #valid of i] or above its non-zero weights -> 1); ties: lower
+ * index.  Y [b, TS], E [b, Bm, TS], mask1 out [b, Bm, TS] (1 = keep).  Needs given and k_rows non-null, TS <= 16384. */
+int mmvid_mp_select_keep_rows(const float* Y, const float* E, const uint8_t* given, const int32_t* k_rows, int b, int Bm, int TS,
+                              uint8_t* mask1, void* stream);
 /* tower input of the b*Bm candidates: control_emb [b, csl, E] broadcast per candidate, then image_emb[id] + tpos with
  * id = mask1 ? (mask1[.] ? I_tok : mask_id) : I_tok.  out [b*Bm, csl+TS, E]. */
 int mmvid_mp_build_input(const float* control_emb, const float* image_emb, int64_t table_rows, const float* tpos,

@@ -1,0 +1,118 @@
+"""Video completion: fill in the unknown tokens of videos whose known part differs from video to video.
+
+The MSM strategies a BERT is trained with hide a box on every frame, its complement, a Bernoulli subset or all but some preserved
+frames (dalle_bert.py:992-1031); at inference the reference reaches two fixed patterns only (`preserve` with long_mode 'long' or
+'interp*'), one pattern and one keep count per call.  Here every row of the batched sampler has its own mask and its own schedule
+(`sampling.mask_predict(given=...)`, one selection kernel for both forms), so one call predicts the rest of a clip from its first
+frames, in-betweens key frames, regenerates a region under a new text -- or does all three in one batch.  The sampler's result for
+a row does not depend on its batch mates.
+
+A known token's value still depends on the pixels AROUND its patch through the VQGAN encoder's receptive field: fill the unknown
+region of `frames` with a constant (the reference's erase_real uses ones) rather than with noise or stale content.
+"""
+import torch
+
+from . import ops
+
+SHAPES = '[b, T] (whole frames), [b, T, h, w] (token grid) or [b, T, H, W] (pixels)'
+
+
+def token_mask(given, T, fmap, image_size):
+    """Which tokens are known -> uint8 [b, T * fmap * fmap] (1 = known), on the device of `given`.  `given` (bool, uint8 or any
+    number, non-zero = known) is [b, T] (whole frames), [b, T, fmap, fmap] (the token grid) or [b, T, image_size, image_size]
+    (pixels).  A token is given only if EVERY pixel of its patch is given."""
+    given = torch.as_tensor(given)
+    T, f, s = int(T), int(fmap), int(image_size)
+    shape = tuple(given.shape)
+    if len(shape) < 2 or shape[1] != T or shape[2:] not in ((), (f, f), (s, s)):
+        raise ValueError(f'given: expected {SHAPES} with T = {T}, h = w = {f}, H = W = {s}; got {shape}')
+    b = shape[0]
+    known = given != 0
+    if shape[2:] == ():
+        known = known.view(b, T, 1).expand(b, T, f * f)
+    elif shape[2:] == (s, s) and s != f:
+        p = s // f
+        known = known.view(b, T, f, p, f, p).all(dim=5).all(dim=3)
+    return known.reshape(b, T * f * f).to(torch.uint8).contiguous()
+
+
+def _frames_to_tokens(model, frames, b):
+    """-> (tokens [b, T * n] int64, real_u8 [b * T, H, W, 3] | None)."""
+    T, n, s = model.num_targets, model.image_seq_len, model.image_size
+    if frames.dim() == 2 and frames.dtype == torch.int64:
+        if tuple(frames.shape) != (b, T * n):
+            raise ValueError(f'frames: token input must be int64 [b, T * n] = [{b}, {T * n}], got {tuple(frames.shape)}')
+        return frames.contiguous(), None
+    if frames.dim() == 5 and frames.dtype == torch.uint8:
+        if tuple(frames.shape) != (b, T, s, s, 3):
+            raise ValueError(f'frames: uint8 input must be [b, T, H, W, 3] = {(b, T, s, s, 3)}, got {tuple(frames.shape)}')
+        real = frames.contiguous().view(b * T, s, s, 3)
+        pixels = ops.frames_u8_to_f32(real).view(b, T, 3, s, s)
+    elif frames.dim() == 5 and frames.dtype == torch.float32:
+        if tuple(frames.shape) != (b, T, 3, s, s):
+            raise ValueError(f'frames: fp32 input must be [b, T, 3, H, W] = {(b, T, 3, s, s)}, got {tuple(frames.shape)}')
+        pixels = frames.contiguous()
+        real = ops.frames_to_u8(pixels.view(b * T, 3, s, s))
+    else:
+        raise ValueError('frames: expected fp32 [b, T, 3, H, W] in [0, 1], uint8 [b, T, H, W, 3] or int64 tokens [b, T * n]; got '
+                         f'{frames.dtype} {tuple(frames.shape)}')
+    return model.get_image_tokens(pixels, reshape=True).contiguous(), real
+
+
+@torch.no_grad()
+def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, mp_config=None, dynamic=True, erase_visual=False,
+             vc_mode=None, face_mode=None, decode=True, paste=True, _race=None, _trace=None):
+    """Complete `b` videos of `num_targets` frames -> (frames_u8 [b, T, H, W, 3] uint8 on the device, or None without `decode`;
+    tokens [b, T, n] int64).
+
+    `frames`: the videos as fp32 [b, T, 3, H, W] in [0, 1], uint8 [b, T, H, W, 3], or int64 tokens [b, T * n]; only what `given`
+    marks is read as known.  Pixels are tokenised by `model.get_image_tokens` in the VQGAN's current `strict` mode; 'split' is the
+    mode whose indices are exact.  `given`: see token_mask; every video may have its own.  `text`, `visual`, `erase_visual`,
+    `vc_mode`, `face_mode`, `mask_predict_steps`, `mp_config`, `dynamic`: as for generate_images.
+
+    One host read precedes the sampler's loop: the number of known tokens per video together with the count of given token ids
+    outside [0, num_image_tokens), which raises ValueError.  `decode` decodes the result once, in slices of `vae._max_frames`;
+    with `paste` and pixel `frames` the known patches show their own pixels and not their VQGAN reconstruction (csrc/frames.hip);
+    with token input there are no pixels to paste and the plain byte kernel runs."""
+    if mp_config is None:
+        raise ValueError('complete: mp_config is required (the schedules of mask-predict, args.mp_config of the reference)')
+    T, n, s, f = model.num_targets, model.image_seq_len, model.image_size, model.image_fmap_size
+    b, dev = text.shape[0], text.device
+    V = model.num_image_tokens
+    if isinstance(visual, (list, tuple)):  # frames [b, 3, H, W] each, as get_image_tokens takes them
+        visual = torch.stack(list(visual), dim=1) if len(visual) else None
+    mask = token_mask(given, T, f, s)
+    if mask.shape[0] != b:
+        raise ValueError(f'given: {mask.shape[0]} rows for {b} videos')
+    was_training = model.training
+    model.eval()
+    try:
+        tokens, real = _frames_to_tokens(model, frames, b)
+        mask = mask.to(tokens.device)
+        known = mask != 0
+        outside = (known & ((tokens < 0) | (tokens >= V))).sum().view(1)
+        stats = torch.cat((known.sum(1), outside)).tolist()  # the one host read: known tokens per video, ids outside the table
+        if stats[-1]:
+            raise ValueError(f'frames: {stats[-1]} given token ids are outside [0, num_image_tokens) = [0, {V})')
+        unknown = [T * n - c for c in stats[:-1]]
+        control = model(text, visual=visual, erase_visual=erase_visual, erase_visual_half=True, vc_mode=vc_mode, face_mode=face_mode,
+                        return_loss=False)
+        mask, tokens = mask.to(dev), tokens.to(dev)
+        seq = model.mask_predict(control, dynamic=dynamic, steps=mask_predict_steps, mp_config=mp_config, given=(mask, tokens),
+                                 _given_unknown=unknown, _race=_race, _trace=_trace)[0]
+        out = None
+        if decode:
+            flat = seq.view(b * T, n)
+            out = torch.empty(b * T, s, s, 3, device=dev, dtype=torch.uint8)
+            grid = mask.view(b * T, f, f)
+            step = model.vae._max_frames(s)
+            for i in range(0, b * T, step):
+                dec = model.vae.decode(flat[i:i + step])
+                if paste and real is not None:
+                    ops.frames_paste_u8(dec, real[i:i + step], grid[i:i + step], out[i:i + step])
+                else:
+                    ops.frames_to_u8(dec, out[i:i + step])
+            out = out.view(b, T, s, s, 3)
+        return out, seq.view(b, T, n)
+    finally:
+        model.train(was_training)

@@ -123,13 +123,18 @@ __global__ __launch_bounds__(256) void sample_race_row_kernel(const float* __res
     }
 }
 
-// grid (Bm, b); dynamic LDS: TS floats
+// grid (Bm, b); dynamic LDS: TS floats.  `preserve` is read with a row stride: 0 = one [TS] mask shared by every video (or null:
+// nothing is preserved), TS = a mask per video; the keep count is k_rows[i] when k_rows is given (a device array, one per video), k
+// otherwise.  Counts, fallback and ranks are per block, so a video's result never depends on its batch mates.
 __global__ __launch_bounds__(256) void mp_select_keep_kernel(const float* __restrict__ Y, const float* __restrict__ E,
-                                                             const unsigned char* __restrict__ preserve, int TS, int Bm,
-                                                             int k, unsigned char* __restrict__ mask1) {
+                                                             const unsigned char* __restrict__ preserve_base, long preserve_stride,
+                                                             int TS, int Bm, int k_value, const int* __restrict__ k_rows,
+                                                             unsigned char* __restrict__ mask1) {
     extern __shared__ float keys[];
     __shared__ int cnt[2];
     const int j = blockIdx.x, i = blockIdx.y;
+    const unsigned char* preserve = preserve_base ? preserve_base + (long)i * preserve_stride : nullptr;
+    const int k = k_rows ? k_rows[i] : k_value;
     const float* y = Y + (long)i * TS;
     const float* e = E + ((long)i * Bm + j) * TS;
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
@@ -494,9 +499,18 @@ extern "C" int mmvid_sample_race_at(const float* logits, int64_t ld, const float
 extern "C" int mmvid_mp_select_keep(const float* Y, const float* E, const uint8_t* preserve, int b, int Bm, int TS, int k,
                                     uint8_t* mask1, void* stream) {
     MMVID_REQUIRE(Y && E && mask1 && b > 0 && Bm > 0 && TS > 0 && TS <= 16384, "mp_select_keep: bad arguments");
-    hipLaunchKernelGGL(mp_select_keep_kernel, dim3(Bm, b), dim3(256), (size_t)TS * 4, (hipStream_t)stream, Y, E, preserve, TS, Bm,
-                       k, mask1);
+    hipLaunchKernelGGL(mp_select_keep_kernel, dim3(Bm, b), dim3(256), (size_t)TS * 4, (hipStream_t)stream, Y, E, preserve, 0L, TS, Bm,
+                       k, (const int*)nullptr, mask1);
     MMVID_LAUNCH_CHECK("mp_select_keep");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_mp_select_keep_rows(const float* Y, const float* E, const uint8_t* given, const int32_t* k_rows, int b, int Bm,
+                                         int TS, uint8_t* mask1, void* stream) {
+    MMVID_REQUIRE(Y && E && given && k_rows && mask1 && b > 0 && Bm > 0 && TS > 0 && TS <= 16384, "mp_select_keep_rows: bad arguments");
+    hipLaunchKernelGGL(mp_select_keep_kernel, dim3(Bm, b), dim3(256), (size_t)TS * 4, (hipStream_t)stream, Y, E, given, (long)TS, TS, Bm,
+                       0, (const int*)k_rows, mask1);
+    MMVID_LAUNCH_CHECK("mp_select_keep_rows");
     return MMVID_OK;
 }
 

@@ -571,7 +571,9 @@ class BERT(nn.Module):
 
     @torch.no_grad()
     def mask_predict(self, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1,
-                     mp_config=None, long_mode='long', _race=None, _trace=None, **kwargs):
-        """dalle_bert.py:514-714, batched over videos and beam candidates on the device (mmvid_amd/sampling.py)."""
+                     mp_config=None, long_mode='long', _race=None, _trace=None, given=None, _given_unknown=None, **kwargs):
+        """dalle_bert.py:514-714, batched over videos and beam candidates on the device (mmvid_amd/sampling.py).  `given` = (mask
+        [b, TS], tokens [b, TS]): per-video known tokens (mmvid_amd/completion.py)."""
         return sampling.mask_predict(self, control_emb, dynamic=dynamic, debug=debug, steps=steps, preserve=preserve,
-                                     t_overlap=t_overlap, mp_config=mp_config, long_mode=long_mode, race=_race, trace=_trace)
+                                     t_overlap=t_overlap, mp_config=mp_config, long_mode=long_mode, race=_race, trace=_trace,
+                                     given=given, given_unknown=_given_unknown)

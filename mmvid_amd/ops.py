@@ -108,6 +108,23 @@ def frames_to_u8(img, out=None):
     return out
 
 
+def frames_paste_u8(img, real, given, out=None):
+    """frames_to_u8 with the known pixels pasted over their reconstruction: img [N, 3, H, W] f32, real [N, H, W, 3] uint8, given
+    [N, h, w] uint8 (non-zero = the token's patch is known) -> [N, H, W, 3] uint8 = given[token of the pixel] ? real : q(img).
+    Needs H % h == 0, W % w == 0 and (W / w) % 4 == 0."""
+    _chk(img, f32, 'img'), _chk(real, torch.uint8, 'real'), _chk(given, torch.uint8, 'given')
+    N, C, H, W = img.shape
+    assert C == 3, f'img: expected [N, 3, H, W], got {tuple(img.shape)}'
+    assert tuple(real.shape) == (N, H, W, 3), f'real: expected {(N, H, W, 3)}, got {tuple(real.shape)}'
+    assert given.dim() == 3 and given.shape[0] == N, f'given: expected [{N}, h, w], got {tuple(given.shape)}'
+    if out is None:
+        out = torch.empty(N, H, W, 3, device=img.device, dtype=torch.uint8)
+    _chk(out, torch.uint8, 'out')
+    assert out.shape == (N, H, W, 3)
+    call('mmvid_frames_paste_u8', _p(img), _p(real), _p(given), N, H, W, given.shape[1], given.shape[2], _p(out), _stream())
+    return out
+
+
 def token_rows_gather(table, frame_index):
     """table [F, n] uint16 on the device (TokenCache.to_device), frame_index [B, T] int64 -> target [B, T*n] int64.  An index
     outside [0, F) reads row 0 and is counted (_lib.check_device_faults)."""
@@ -604,10 +621,18 @@ def sample_race(logits, E, noise_u=None, temperature=0.0, logit_div=1.0, tok_off
 
 
 def mp_select_keep(Y, E, preserve, k):
-    """Y [b, TS], E [b, Bm, TS], preserve [TS] uint8 or None -> mask1 [b, Bm, TS] uint8 (1 = position stays visible)."""
+    """Y [b, TS], E [b, Bm, TS], preserve [TS] uint8 or None -> mask1 [b, Bm, TS] uint8 (1 = position stays visible).
+    A 2-D preserve [b, TS] with a tensor k (int32 [b] on the device) is the per-video form: row i has its own mask and keep count."""
     _chk(Y, f32, 'Y'), _chk(E, f32, 'E')
     b, Bm, TS = E.shape
     mask1 = torch.empty(b, Bm, TS, device=Y.device, dtype=u8)
+    if torch.is_tensor(k) or (preserve is not None and preserve.dim() == 2):
+        if not torch.is_tensor(k) or preserve is None or preserve.dim() != 2:
+            raise ValueError('mp_select_keep: the per-video form takes preserve [b, TS] uint8 AND k int32 [b] on the device')
+        _chk(preserve, u8, 'preserve'), _chk(k, torch.int32, 'k')
+        assert tuple(preserve.shape) == (b, TS) and tuple(k.shape) == (b, ), (tuple(preserve.shape), tuple(k.shape), (b, TS))
+        call('mmvid_mp_select_keep_rows', _p(Y), _p(E), _p(preserve), _p(k), b, Bm, TS, _p(mask1), _stream())
+        return mask1
     call('mmvid_mp_select_keep', _p(Y), _p(E), _p(preserve), b, Bm, TS, int(k), _p(mask1), _stream())
     return mask1
 

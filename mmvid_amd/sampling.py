@@ -8,6 +8,9 @@ when `dynamic` is set.
 
 Results are a function of the Exp(1) race variates (ops.exponential_like in production; tests inject them), of the
 schedule and of the model -- independent of how many videos share the call.
+
+`given` (video completion, mmvid_amd/completion.py) tells the sampler which tokens of which video are known: a mask and
+a keep-count schedule PER ROW, where `preserve` has one pattern and one count for the whole call.
 """
 import numpy as np
 import torch
@@ -51,22 +54,71 @@ def preserved_tokens(model, b, preserve, t_overlap, long_mode, device):
     return TS, None, fixed_tok
 
 
+def keep_table(mp_config, unknown, Tmax):
+    """Keep counts of a call with per-row given tokens -> int32 [Tmax - 1, b] (host): entry [t - 1, i] is the k of step t for row i,
+    `unknown[i] - schedule(mp_config, unknown[i])[0][t - 1]`, with `unknown[i]` the row's number of unknown positions.  `schedule` runs
+    once per distinct count."""
+    per_count = {N: schedule(mp_config, N)[0] for N in sorted(set(int(v) for v in unknown))}
+    table = np.empty((Tmax - 1, len(unknown)), np.int32)
+    for i, N in enumerate(unknown):
+        table[:, i] = [int(N) - per_count[int(N)][t - 1] for t in range(1, Tmax)]
+    return table
+
+
+def given_tokens(model, b, given, given_unknown, device):
+    """`given` = (mask [b, TS] uint8 / bool, 1 = known; tokens [b, TS] int64) -> (unknown positions per row (host list), mask uint8
+    [b, TS] on the device, fixed_tok [b, TS]: the given tokens, [MASK] elsewhere).  The per-row counts are the one host read of the
+    given path: a mask on the host makes it free, a mask on the device costs one sync before the loop, and a caller that already
+    holds the counts passes them as `given_unknown`."""
+    TS, MASK = model.target_seq_len, model.image_token_lut['[MASK]']
+    if not isinstance(given, (tuple, list)) or len(given) != 2:
+        raise ValueError('given: expected (mask [b, TS] uint8 or bool, tokens [b, TS] int64)')
+    mask, tokens = given
+    if tuple(mask.shape) != (b, TS) or mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f'given: the mask must be uint8 or bool [b, TS] = [{b}, {TS}], got {mask.dtype} {tuple(mask.shape)}')
+    if tuple(tokens.shape) != (b, TS) or tokens.dtype != torch.int64:
+        raise ValueError(f'given: the tokens must be int64 [b, TS] = [{b}, {TS}], got {tokens.dtype} {tuple(tokens.shape)}')
+    known = mask != 0
+    if given_unknown is None:
+        given_unknown = (TS - known.sum(1)).tolist()
+    if len(given_unknown) != b:
+        raise ValueError(f'given: {len(given_unknown)} row counts for {b} rows')
+    known = known.to(device)
+    fixed_tok = torch.where(known, tokens.to(device), torch.full((), MASK, dtype=torch.long, device=device)).contiguous()
+    return [int(v) for v in given_unknown], known.to(torch.uint8).contiguous(), fixed_tok
+
+
 @torch.no_grad()
 def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1, mp_config=None,
-                 long_mode='long', race=None, trace=None):
+                 long_mode='long', race=None, trace=None, given=None, given_unknown=None):
     """-> (tokens [b, TS] int64, image_samples list).  `race(name, shape)` supplies the Exp(1) variates (default: the
-    device generator); `trace` (a list) receives one dict of the step's tensors per step (tests)."""
+    device generator); `trace` (a list) receives one dict of the step's tensors per step (tests).
+
+    `given` = (mask [b, TS] uint8 / bool, tokens [b, TS] int64): the tokens of row i where mask[i] is 1 are known.  They hold their
+    value from step 0 on, are visible to the tower in every candidate and are never re-masked; row i runs the schedule of its own
+    N_i = TS - sum(mask[i]) unknown positions (keep count of step t: N_i - n_i[t - 1], read by the kernel from one device table built
+    before the loop).  A row with nothing unknown returns its tokens, a row with nothing given is the plain sampler's.  Exclusive
+    with `preserve` and the interp modes, which are the two shared patterns of this.  See given_tokens for the one host read."""
     dev = control_emb.device
     b, csl, E = control_emb.shape
     TS, MASK, V = model.target_seq_len, model.image_token_lut['[MASK]'], model.num_image_tokens
     L = csl + TS
     draw = race if race is not None else (lambda name, shape: ops.exponential_like(shape, dev))
-    N, fixed, fixed_tok = preserved_tokens(model, b, preserve, t_overlap, long_mode, dev)
-    n, temp = schedule(mp_config, N)
     Tmax = mp_config['T'] if steps <= 0 else steps
     Bm = mp_config['B']
     if Tmax < 2:
         raise RuntimeError('mask_predict needs at least 2 steps (the reference returns nothing for steps == 1)')
+    if given is None:
+        N, fixed, fixed_tok = preserved_tokens(model, b, preserve, t_overlap, long_mode, dev)
+        n, temp = schedule(mp_config, N)
+        keep_count = lambda t: N - n[t - 1]  # noqa: E731
+    else:
+        if preserve is not None or long_mode != 'long':
+            raise ValueError("given: exclusive with `preserve` and with long_mode != 'long' (both are fixed patterns of given tokens)")
+        unknown, fixed, fixed_tok = given_tokens(model, b, given, given_unknown, dev)
+        temp = schedule(mp_config, TS)[1]  # (the temperature schedule does not depend on N)
+        k_table = torch.from_numpy(keep_table(mp_config, unknown, Tmax)).to(dev)
+        keep_count = lambda t: k_table[t - 1]  # noqa: E731
 
     control_emb = ops._chk(control_emb.contiguous().float(), torch.float32, 'control_emb')
     iemb = model.image_emb.weight.detach()
@@ -106,7 +158,7 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
 
     for t in range(1, Tmax):
         Ek = draw(f'keep{t}', (b, Bm, TS))
-        mask1 = ops.mp_select_keep(Y, Ek, fixed, N - n[t - 1])
+        mask1 = ops.mp_select_keep(Y, Ek, fixed, keep_count(t))
         out, logits = tower_logits(I_tok, mask1, Bm)
         Et = draw(f'tok{t}', (b * Bm * TS, V))
         Inew, Ynew = ops.sample_race(logits, Et, noise(f'tok{t}', t, (b * Bm * TS, V)), temp[t])
@@ -117,7 +169,7 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
                                   vid_head[1].bias, vid_head[0].eps)[0]
         rec = None
         if trace is not None or debug:
-            rec = dict(t=t, k=N - n[t - 1], E_keep=Ek, mask1=mask1, logits=logits, E_tok=Et, Ynew=Ynew.view(b, Bm, TS),
+            rec = dict(t=t, k=keep_count(t), E_keep=Ek, mask1=mask1, logits=logits, E_tok=Et, Ynew=Ynew.view(b, Bm, TS),
                        Inew=Inew.view(b, Bm, TS), z_rel=z_rel, z_vid=z_vid, Y_before=Y.clone(), I_before=I_tok.clone(),
                        active_before=active.clone(), S=torch.empty(b, Bm, device=dev),
                        jmax=torch.empty(b, dtype=torch.int32, device=dev))
