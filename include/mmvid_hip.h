@@ -233,6 +233,14 @@ int mmvid_msm_masks(uint64_t seed, const float* step_dev, int B, int T, int f, c
  * [B, T*f*f] uint8 = the Bernoulli field of strategy 1 (may be NULL when no sample uses it). */
 int mmvid_msm_masks_inject(const int32_t* decisions, const uint8_t* bernoulli, int B, int T, int f, uint8_t* mask1,
                            float* not_fully_masked, void* stream);
+/* Condition drop for classifier-free guidance (train.py:302 --dropout_vc, dalle_bert.py:954-958 for the visual; 917-919 for the
+ * text): sample b's text [B, Tt] becomes all 0 (pad) with probability p_text, its visual tokens [B, Vs] all mask_id with probability
+ * p_visual, on two streams of their own keyed (seed, step, sample, purpose) like the rest (state_dev as step_dev above).  inject
+ * [B, 2] uint8 (optional) = {drop text, drop visual} replaces the draws (tests).  vis_tok may be NULL (no visual control: vis_out is
+ * not written).  Out of place: text_out [B, Tt], vis_out [B, Vs]; decided [B, 2] uint8 receives the decisions. */
+int mmvid_cond_drop(const int64_t* text, const int64_t* vis_tok, int B, int Tt, int Vs, const float* state_dev, uint64_t seed,
+                    float p_text, float p_visual, const uint8_t* inject, int64_t mask_id, int64_t* text_out, int64_t* vis_out,
+                    uint8_t* decided, void* stream);
 /* VID negative, dalle_bert.py:204-238 (+93-202): x, out [B,T,C,H,W] fp32 in [0,1]; strategy_prob[4] = frame of another
  * sample | frame shuffle | colour shift | affine warp (affine_grid + bilinear grid_sample, reflection padding).
  * params_scratch: B * mmvid_warp_params_bytes() bytes; draw_params = 0 applies the parameters already in it (tests). */
@@ -471,6 +479,13 @@ int mmvid_sample_race(const float* logits, int64_t ld, const float* E, const flo
 int mmvid_sample_race_at(const float* logits, int64_t ld, const float* E, const int32_t* step_dev, int step0, int64_t e_step_stride,
                          const float* noise_u, float temperature, float logit_div, int64_t R, int V, int64_t tok_offset, int64_t* tok,
                          float* y, void* stream);
+/* Classifier-free guidance on the wave-per-row draw (dalle_bert.py:527-534 with two logit rows): the value that enters the pipeline
+ * above for row r, class c is g = lc + w * (lc - lu), w = scale_dev[r / rows_per_scale] -- three separately rounded fp32 operations
+ * (subtract, multiply, add; never an FMA), and lc == -inf gives -inf.  logits_c and logits_u [R, V] share ld; scale_dev is fp32
+ * [R / rows_per_scale] on the device; R % rows_per_scale == 0.  tok, y (may be NULL) as for mmvid_sample_race.  No atomics. */
+int mmvid_sample_race_guided(const float* logits_c, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
+                             const float* E, const float* noise_u, float temperature, float logit_div, int64_t R, int V,
+                             int64_t tok_offset, int64_t* tok, float* y, void* stream);
 /* keep-mask of a refinement step (dalle_bert.py:646-668): of the positions with preserve == 0, the k with the smallest
  * E / Y stay visible (k outside [1, #non-zero weights] -> 1, the reference's except branch); preserved positions always
  * stay.  Y [b, TS], E [b, Bm, TS], mask1 out [b, Bm, TS] (1 = keep). */

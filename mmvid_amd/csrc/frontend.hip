@@ -51,7 +51,8 @@ __device__ __forceinline__ Rng make_rng(uint64_t seed, const float* step_dev, in
     g.sample = (uint32_t)sample, g.purpose = (uint32_t)purpose;
     return g;
 }
-enum { P_STRATEGY = 1, P_BERNOULLI = 2, P_BOX = 3, P_PC = 4, P_WARP = 5, P_PERM = 6, P_ERASE = 7, P_FACE = 8, P_VCOLOR = 9 };
+enum { P_STRATEGY = 1, P_BERNOULLI = 2, P_BOX = 3, P_PC = 4, P_WARP = 5, P_PERM = 6, P_ERASE = 7, P_FACE = 8, P_VCOLOR = 9,
+       P_NULL_TEXT = 10, P_NULL_VISUAL = 11 };
 
 // torchvision.transforms.RandomErasing.get_params (third-party, absent from /root/reference; restated from the
 // published semantics): up to 10 attempts of { area*U(scale), exp(U(log ratio)) -> h, w = round(sqrt(..)) ; accept if
@@ -482,6 +483,35 @@ __global__ __launch_bounds__(256) void visual_color_kernel(uint64_t seed, const 
     x[idx] = fminf(fmaxf(x[idx] + m, 0.f), 1.f);
 }
 
+// ---- condition drop for classifier-free guidance: one block per sample.  With probability p_text the sample's text becomes all pad
+// (0: bert_build_ids maps it to the per-position pad ids, dalle_bert.py:917-919), with probability p_visual its visual tokens become
+// all [MASK], [SEP] slots included -- what visual=None gives (dalle_bert.py:954-958; train.py:302 --dropout_vc).  Two streams of their
+// own: no other decision of the step moves.  `inject` [B, 2] replaces the draws (tests).  Out of place: the inputs may be the caller's.
+__global__ __launch_bounds__(256) void cond_drop_kernel(uint64_t seed, const float* __restrict__ step_dev,
+                                                        const long long* __restrict__ text, const long long* __restrict__ vis_tok, int Tt,
+                                                        int Vs, float p_text, float p_visual, const unsigned char* __restrict__ inject,
+                                                        long long mask_id, long long* __restrict__ text_out,
+                                                        long long* __restrict__ vis_out, unsigned char* __restrict__ decided) {
+    __shared__ int s_drop[2];
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        int dt, dv;
+        if (inject) {
+            dt = inject[2 * b] ? 1 : 0, dv = inject[2 * b + 1] ? 1 : 0;
+        } else {
+            dt = make_rng(seed, step_dev, b, P_NULL_TEXT).uniform(0) < p_text ? 1 : 0;
+            dv = make_rng(seed, step_dev, b, P_NULL_VISUAL).uniform(0) < p_visual ? 1 : 0;
+        }
+        s_drop[0] = dt, s_drop[1] = dv;
+        decided[2 * b] = (unsigned char)dt, decided[2 * b + 1] = (unsigned char)dv;
+    }
+    __syncthreads();
+    const bool dt = s_drop[0] != 0, dv = s_drop[1] != 0;
+    for (int i = threadIdx.x; i < Tt; i += 256) text_out[(long)b * Tt + i] = dt ? 0 : text[(long)b * Tt + i];
+    if (vis_tok)
+        for (int i = threadIdx.x; i < Vs; i += 256) vis_out[(long)b * Vs + i] = dv ? mask_id : vis_tok[(long)b * Vs + i];
+}
+
 __global__ void counter_add_kernel(float* c, float v) {
     if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += v;
 }
@@ -663,6 +693,20 @@ extern "C" int mmvid_visual_color_jitter(uint64_t seed, const float* step_dev, f
     hipLaunchKernelGGL(visual_color_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, seed, step_dev, B, Tv, C,
                        (long)H * W, p, first_frame, x, params_out);
     MMVID_LAUNCH_CHECK("visual_color_jitter");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_cond_drop(const int64_t* text, const int64_t* vis_tok, int B, int Tt, int Vs, const float* state_dev, uint64_t seed,
+                               float p_text, float p_visual, const uint8_t* inject, int64_t mask_id, int64_t* text_out, int64_t* vis_out,
+                               uint8_t* decided, void* stream) {
+    MMVID_REQUIRE(text && text_out && decided && B > 0 && Tt > 0 && Vs >= 0, "cond_drop: bad arguments");
+    MMVID_REQUIRE(!vis_tok || (vis_out && Vs > 0), "cond_drop: visual tokens need vis_out and Vs > 0");
+    MMVID_REQUIRE(p_text >= 0.f && p_text <= 1.f && p_visual >= 0.f && p_visual <= 1.f, "cond_drop: p_text=%g p_visual=%g outside [0, 1]",
+                  (double)p_text, (double)p_visual);
+    hipLaunchKernelGGL(cond_drop_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, seed, state_dev, (const long long*)text,
+                       (const long long*)vis_tok, Tt, Vs, p_text, p_visual, inject, (long long)mask_id, (long long*)text_out,
+                       (long long*)vis_out, decided);
+    MMVID_LAUNCH_CHECK("cond_drop");
     return MMVID_OK;
 }
 

@@ -24,8 +24,25 @@ __device__ __forceinline__ Best better(Best a, Best b) {
     return (b.key < a.key || (b.key == a.key && b.idx < a.idx)) ? b : a;
 }
 
-// one wave per row
-__global__ __launch_bounds__(256) void sample_race_kernel(const float* __restrict__ logits, long ld,
+// Classifier-free guidance: the value that enters the race is lc + w * (lc - lu), lc / lu the logits under the conditional / the
+// unconditional control.  Three separately rounded fp32 operations, so the result is the function of (lc, lu, w) that three
+// elementwise tensor operations give, bit for bit: contraction is off for the operators of this function and stays off where it is
+// inlined (the __fmul_rn / __fadd_rn wrappers carry their header's contraction setting with them and DO fuse into one v_fmac here).
+// A class the conditional branch rules out stays ruled out whatever w and lu are.
+__device__ __forceinline__ float guided_logit(float lc, float lu, float w) {
+#pragma clang fp contract(off)
+    if (lc == -INFINITY) return -INFINITY;
+    const float d = lc - lu;
+    const float m = w * d;
+    return lc + m;
+}
+
+// one wave per row.  GUIDED: `logits` is the conditional branch, logits_u (same ld) the unconditional one, and row r takes its
+// scale from scale_dev[r / rows_per_scale]; everything after the logit is the same code, so the guided draw on (lc, lu, w) is the
+// plain draw on guided_logit(lc, lu, w).
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void sample_race_kernel(const float* __restrict__ logits, const float* __restrict__ logits_u, long ld,
+                                                          const float* __restrict__ scale_dev, long rows_per_scale,
                                                           const float* __restrict__ E, const float* __restrict__ noise_u,
                                                           float temperature, float inv_temp_div, long R, int V,
                                                           long long tok_offset, long long* __restrict__ tok_out,
@@ -34,10 +51,12 @@ __global__ __launch_bounds__(256) void sample_race_kernel(const float* __restric
     if (r >= R) return;
     const int lane = threadIdx.x & 63;
     const float* x = logits + r * ld;
+    const float* xu = GUIDED ? logits_u + r * ld : nullptr;
+    const float w = GUIDED ? scale_dev[r / rows_per_scale] : 0.f;
     const float* e = E + r * (long)V;
     const float* g = noise_u ? noise_u + r * (long)V : nullptr;
     auto xv = [&](int c) -> float {
-        float v = x[c] * inv_temp_div;  // ART-V divides the logits by the temperature (dalle_artv.py:275)
+        float v = (GUIDED ? guided_logit(x[c], xu[c], w) : x[c]) * inv_temp_div;  // ART-V divides the logits by the temperature (dalle_artv.py:275)
         if (g) v += temperature * gumbel_from_u(g[c]);  // BERT adds temperature-scaled Gumbel noise (dalle_bert.py:528)
         return v;
     };
@@ -489,10 +508,28 @@ extern "C" int mmvid_sample_race_at(const float* logits, int64_t ld, const float
                            (long)e_step_stride, 1.0f / logit_div, V, (long long)tok_offset, (long long*)tok);
     } else {
         MMVID_REQUIRE(!step_dev, "sample_race_at: a device-side draw index needs the token-only form (no y, no noise, R <= 1024)");
-        hipLaunchKernelGGL(sample_race_kernel, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, E, noise_u,
-                           temperature, 1.0f / logit_div, (long)R, V, (long long)tok_offset, (long long*)tok, y);
+        hipLaunchKernelGGL(sample_race_kernel<false>, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, logits, (const float*)nullptr,
+                           (long)ld, (const float*)nullptr, 1L, E, noise_u, temperature, 1.0f / logit_div, (long)R, V, (long long)tok_offset,
+                           (long long*)tok, y);
     }
     MMVID_LAUNCH_CHECK("sample_race");
+    return MMVID_OK;
+}
+
+// The wave-per-row draw on lc + w * (lc - lu), w = scale_dev[r / rows_per_scale] (see guided_logit): one pass over both logit
+// tensors, nothing written but tok and y.
+extern "C" int mmvid_sample_race_guided(const float* logits_c, const float* logits_u, int64_t ld, const float* scale_dev,
+                                        int64_t rows_per_scale, const float* E, const float* noise_u, float temperature, float logit_div,
+                                        int64_t R, int V, int64_t tok_offset, int64_t* tok, float* y, void* stream) {
+    MMVID_REQUIRE(logits_c && logits_u && scale_dev && E && tok && R >= 0 && V > 0 && ld >= V, "sample_race_guided: bad arguments");
+    MMVID_REQUIRE(logit_div > 0.f, "sample_race_guided: logit_div (the softmax temperature divisor) must be > 0");
+    MMVID_REQUIRE(rows_per_scale > 0 && R % rows_per_scale == 0, "sample_race_guided: R=%ld is no multiple of rows_per_scale=%ld", (long)R,
+                  (long)rows_per_scale);
+    if (R == 0) return MMVID_OK;
+    hipLaunchKernelGGL(sample_race_kernel<true>, dim3(cdiv(R, 4)), dim3(256), 0, (hipStream_t)stream, logits_c, logits_u, (long)ld,
+                       scale_dev, (long)rows_per_scale, E, noise_u, temperature, 1.0f / logit_div, (long)R, V, (long long)tok_offset,
+                       (long long*)tok, y);
+    MMVID_LAUNCH_CHECK("sample_race_guided");
     return MMVID_OK;
 }
 

@@ -23,7 +23,7 @@ from torch import nn
 
 from . import ops, sampling
 from .clip_tower import OpenAICLIPTransformer
-from .frontend import Frontend, face_choices
+from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import PosTable, AssembleSequence, BertHeads, LNLinear, Linear, LayerNormRows
 from .modules import AxialPositionalEmbedding, AxialPositionalEmbeddingList
 
@@ -435,11 +435,17 @@ class BERT(nn.Module):
                 erase_visual=False, erase_visual_half=False, msm_strategy_prob=[0.7, 0.1, 0.1, 0.1],
                 msm_bernoulli_prob=[0.2, 0.5], rel_no_fully_masked=False,
                 vid_strategy_prob=[0.25, 0.25, 0.25, 0.25], negvc=False, visual_neg=None, text_neg=None, pc_prob=0,
-                vc_mode=None, face_mode=None, visual_aug_mode=None, _mask1=None, _target_warp=None, target_frames=None, **kwargs):
+                vc_mode=None, face_mode=None, visual_aug_mode=None, _mask1=None, _target_warp=None, target_frames=None,
+                null_text_prob=0.0, null_visual_prob=0.0, _null=None, **kwargs):
         """`target` is the video [B, T, 3, H, W] in [0, 1], or its tokens [B, T*n] int64 (training from a token cache: the VQGAN is
         frozen and the default transform is deterministic, so a frame's tokens never change).  With token targets and `vid`, the VID
         negative still needs the pixels of ONE frame per sample when the colour-shift or affine strategy is drawn: pass
-        `target_frames`, the same frames as uint8 [B, T, H, W, 3] or fp32 [B, T, 3, H, W] (see _token_target_negative)."""
+        `target_frames`, the same frames as uint8 [B, T, H, W, 3] or fp32 [B, T, 3, H, W] (see _token_target_negative).
+
+        `null_text_prob` / `null_visual_prob` (training for classifier-free guidance): each sample's text becomes all pad, and its
+        visual control all [MASK] (what visual=None gives), with these probabilities, drawn on the device before the ids are built
+        (Frontend.cond_drop); `_null` (uint8 [B, 2]) injects the decisions (tests).  Both 0 and no `_null`: nothing is launched."""
+        drop = check_condition_drop(null_text_prob, null_visual_prob, self.fixed_language_model is not None, return_loss, _null is not None)
         device = text.device
         B = text.shape[0]
         text_rows = None
@@ -458,6 +464,9 @@ class BERT(nn.Module):
         MASK = self.image_token_lut['[MASK]']
         pad_base = self.num_text_tokens - self.text_seq_len
         vis_tok = self._visual_tokens(visual, erase_visual, erase_visual_half, vc_mode, face_mode, visual_aug_mode)
+        if drop:  # before the ids: the REL negative (halves swapped) and the VID pass see the dropped control; text_neg is not touched
+            text, vis_tok = self.frontend.cond_drop(text, vis_tok.contiguous() if vis_tok is not None else None, null_text_prob,
+                                                    null_visual_prob, MASK, _null)
         if not return_loss:  # control embedding only (dalle_bert.py:977-978)
             empty = torch.empty(B, 0, dtype=torch.long, device=device)
             ids = ops.bert_build_ids(text, vis_tok, self.visual_seq_len, empty, None, torch.empty(B, 0, dtype=torch.uint8, device=device),
@@ -558,10 +567,18 @@ class BERT(nn.Module):
     @eval_decorator
     def generate_images(self, text, *, visual=None, mask=None, img=None, argmax=False, dynamic=True, debug=False,
                         erase_visual=False, mask_predict_steps=10, preserve=None, t_overlap=1, pc_mode=None,
-                        vc_mode=None, face_mode=None, mp_config=None, long_mode='long', **kwargs):
-        """dalle_bert.py:434-487 -> (images [b,T,3,H,W], pnag_samples, img_seq [(b T), n])."""
+                        vc_mode=None, face_mode=None, mp_config=None, long_mode='long', guidance_scale=None,
+                        guidance_drop=('text', 'visual'), negative_text=None, **kwargs):
+        """dalle_bert.py:434-487 -> (images [b,T,3,H,W], pnag_samples, img_seq [(b T), n]).  `guidance_scale` (a float, one per step,
+        one per video or [steps, b]: sampling.guidance_table) switches classifier-free guidance on; see guidance_control for
+        `guidance_drop` and `negative_text`."""
+        drop = sampling.check_guidance(self.num_visuals, self.fixed_language_model is not None, guidance_scale, guidance_drop,
+                                       negative_text)
         control_emb = self(text, visual=visual, erase_visual=erase_visual, erase_visual_half=True, vc_mode=vc_mode,
                            face_mode=face_mode, return_loss=False)
+        if drop is not None:
+            kwargs.update(guidance_scale=guidance_scale, uncond_emb=self.guidance_control(
+                text, drop, negative_text, visual=visual, erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode))
         img_seq, pnag_samples = self.mask_predict(control_emb, argmax=argmax, dynamic=dynamic, debug=debug,
                                                   steps=mask_predict_steps, preserve=preserve, t_overlap=t_overlap,
                                                   pc_mode=pc_mode, mp_config=mp_config, long_mode=long_mode, **kwargs)
@@ -570,10 +587,27 @@ class BERT(nn.Module):
         return images.view(-1, self.num_targets, *images.shape[1:]), pnag_samples, img_seq
 
     @torch.no_grad()
+    def guidance_control(self, text, drop, negative_text=None, *, visual=None, erase_visual=False, vc_mode=None, face_mode=None):
+        """The unconditional control of a guided call: one more control-only forward (the front-end step counter advances once more).
+        Its text is `negative_text` when given, all pad when `drop` names 'text', else `text`; its visual control is None (all [MASK])
+        when `drop` names 'visual', else `visual` with the same erase_visual / vc_mode / face_mode.  `drop`: sampling.check_guidance."""
+        if negative_text is not None:
+            if self.fixed_language_model is None and (tuple(negative_text.shape) != tuple(text.shape) or negative_text.dtype != torch.int64):
+                raise ValueError(f'negative_text: expected int64 {tuple(text.shape)} like text, got {negative_text.dtype} '
+                                 f'{tuple(negative_text.shape)}')
+            text_u = negative_text.to(text.device)
+        else:
+            text_u = torch.zeros_like(text) if 'text' in drop else text
+        return self(text_u, visual=None if 'visual' in drop else visual, erase_visual=erase_visual, erase_visual_half=True,
+                    vc_mode=vc_mode, face_mode=face_mode, return_loss=False)
+
+    @torch.no_grad()
     def mask_predict(self, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1,
-                     mp_config=None, long_mode='long', _race=None, _trace=None, given=None, _given_unknown=None, **kwargs):
+                     mp_config=None, long_mode='long', _race=None, _trace=None, given=None, _given_unknown=None, uncond_emb=None,
+                     guidance_scale=None, **kwargs):
         """dalle_bert.py:514-714, batched over videos and beam candidates on the device (mmvid_amd/sampling.py).  `given` = (mask
-        [b, TS], tokens [b, TS]): per-video known tokens (mmvid_amd/completion.py)."""
+        [b, TS], tokens [b, TS]): per-video known tokens (mmvid_amd/completion.py).  `uncond_emb` [b, csl, E] with `guidance_scale`:
+        classifier-free guidance (sampling.mask_predict)."""
         return sampling.mask_predict(self, control_emb, dynamic=dynamic, debug=debug, steps=steps, preserve=preserve,
                                      t_overlap=t_overlap, mp_config=mp_config, long_mode=long_mode, race=_race, trace=_trace,
-                                     given=given, given_unknown=_given_unknown)
+                                     given=given, given_unknown=_given_unknown, uncond_emb=uncond_emb, guidance_scale=guidance_scale)

@@ -18,6 +18,21 @@ def _farr(vals):
     return (ctypes.c_float * len(vals))(*[float(v) for v in vals])
 
 
+def check_condition_drop(null_text_prob, null_visual_prob, fixed_language_model=False, return_loss=True, injected=False):
+    """The argument rules of the training-side condition drop (BERT.forward's null_text_prob / null_visual_prob / _null), before any
+    device work -> True when the drop kernel has to run."""
+    for name, p in (('null_text_prob', null_text_prob), ('null_visual_prob', null_visual_prob)):
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f'{name} = {p}: a probability in [0, 1]')
+    on = float(null_text_prob) > 0 or float(null_visual_prob) > 0 or injected
+    if on and not return_loss:
+        raise ValueError('null_text_prob / null_visual_prob / _null belong to the training forward; the control-only call '
+                         '(return_loss=False) takes the control it is given (generate_images builds the unconditional one)')
+    if fixed_language_model and float(null_text_prob) > 0:
+        raise ValueError('null_text_prob > 0 with a fixed language model: there is no defined null sentence feature')
+    return on
+
+
 class Frontend:
     """`state` is a device buffer of four 32-bit words: [0] the forward-call counter (fp32, advanced by a device op), [1..2]
     the 64-bit seed, [3] reserved.  The kernels read the seed from there (their by-value seed argument is XORed on top and
@@ -30,6 +45,7 @@ class Frontend:
         self.state = None  # created on first use, on the device of that use
         self._pending_step = None
         self._warp_scratch = None
+        self.last_null = None  # uint8 [B, 2] on the device: {text dropped, visual dropped} of the last cond_drop (tests)
 
     # ---- seed / step live on the device once `state` exists
     @staticmethod
@@ -119,6 +135,31 @@ class Frontend:
         _lib.call('mmvid_msm_masks_inject', _p(ops._chk(decisions, torch.int32, 'decisions')), _p(bernoulli), B, T, fmap, _p(mask1),
                   _p(nfm), _stream())
         return mask1, nfm
+
+    def cond_drop(self, text, vis_tok, p_text, p_visual, mask_id, inject=None):
+        """Condition drop for classifier-free guidance: text [B, Tt] int64, vis_tok [B, Vs] int64 or None -> (text', vis_tok' | None), new
+        tensors in which a dropped sample's text is all 0 (pad) and its visual tokens are all `mask_id`.  Sample b drops its text with
+        probability p_text and its visual control with probability p_visual, on two streams of the step's generator that nothing else
+        reads; `inject` (uint8 [B, 2]) replaces the draws (tests).  The decisions stay in `last_null`."""
+        check_condition_drop(p_text, p_visual)
+        ops._chk(text, i64, 'text')
+        B, Tt = text.shape
+        Vs = 0
+        if vis_tok is not None:
+            ops._chk(vis_tok, i64, 'vis_tok')
+            assert vis_tok.dim() == 2 and vis_tok.shape[0] == B, (tuple(vis_tok.shape), B)
+            Vs = vis_tok.shape[1]
+        if inject is not None:
+            inject = ops._chk(inject.to(device=text.device, dtype=u8).contiguous(), u8, 'inject')
+            if tuple(inject.shape) != (B, 2):
+                raise ValueError(f'cond_drop: inject must be uint8 [B, 2] = [{B}, 2], got {tuple(inject.shape)}')
+        text_out = torch.empty_like(text)
+        vis_out = torch.empty_like(vis_tok) if vis_tok is not None else None
+        decided = torch.empty(B, 2, device=text.device, dtype=u8)
+        _lib.call('mmvid_cond_drop', _p(text), _p(vis_tok), B, Tt, Vs, _p(self._step(text.device)), 0, float(p_text), float(p_visual),
+                  _p(inject), int(mask_id), _p(text_out), _p(vis_out), _p(decided), _stream())
+        self.last_null = decided
+        return text_out, vis_out
 
     def vid_warp(self, x, strategy_prob, out=None, params=None):
         """x [B,T,C,H,W] f32 in [0,1] -> the VID negative.  `params` (a uint8 tensor of B * warp_params_bytes): apply

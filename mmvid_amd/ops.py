@@ -620,6 +620,29 @@ def sample_race(logits, E, noise_u=None, temperature=0.0, logit_div=1.0, tok_off
     return tok, y
 
 
+def sample_race_guided(logits_c, logits_u, scale, rows_per_scale, E, noise_u=None, temperature=0.0, logit_div=1.0):
+    """sample_race on lc + w * (lc - lu) (three rounded fp32 operations, lc == -inf stays -inf), w = scale[r // rows_per_scale]: logits_c,
+    logits_u [R, V] f32 with one row stride, scale f32 [R // rows_per_scale] on the device -> (tok int64 [R], y f32 [R])."""
+    _chk(E, f32, 'E'), _chk(scale, f32, 'scale')
+    assert logits_c.dtype == f32 and logits_c.is_cuda and logits_c.stride(1) == 1
+    assert logits_u.dtype == f32 and logits_u.is_cuda and logits_u.stride(1) == 1
+    R, V = logits_c.shape
+    if tuple(logits_u.shape) != (R, V) or logits_u.stride(0) != logits_c.stride(0):
+        raise ValueError(f'sample_race_guided: logits_u {tuple(logits_u.shape)} (row stride {logits_u.stride(0)}) must have the shape and '
+                         f'the row stride of logits_c {(R, V)} ({logits_c.stride(0)})')
+    assert E.shape == (R, V) and E.is_contiguous()
+    rows_per_scale = int(rows_per_scale)
+    if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
+        raise ValueError(f'sample_race_guided: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
+    tok = torch.empty(R, device=logits_c.device, dtype=i64)
+    y = torch.empty(R, device=logits_c.device, dtype=f32)
+    if noise_u is not None:
+        _chk(noise_u, f32, 'noise_u')
+    call('mmvid_sample_race_guided', _p(logits_c), _p(logits_u), logits_c.stride(0), _p(scale), rows_per_scale, _p(E), _p(noise_u),
+         float(temperature), float(logit_div), R, V, 0, _p(tok), _p(y), _stream())
+    return tok, y
+
+
 def mp_select_keep(Y, E, preserve, k):
     """Y [b, TS], E [b, Bm, TS], preserve [TS] uint8 or None -> mask1 [b, Bm, TS] uint8 (1 = position stays visible).
     A 2-D preserve [b, TS] with a tensor k (int32 [b] on the device) is the per-video form: row i has its own mask and keep count."""

@@ -11,6 +11,10 @@ schedule and of the model -- independent of how many videos share the call.
 
 `given` (video completion, mmvid_amd/completion.py) tells the sampler which tokens of which video are known: a mask and
 a keep-count schedule PER ROW, where `preserve` has one pattern and one count for the whole call.
+
+Classifier-free guidance (`uncond_emb`, `guidance_scale`): every step runs the tower a second time on the same tokens under the
+unconditional control, and the token race reads `lc + w * (lc - lu)` from the two logit tensors in one kernel
+(ops.sample_race_guided).  Scores, candidate choice, the dynamic stop and the given tokens belong to the conditional branch alone.
 """
 import numpy as np
 import torch
@@ -88,9 +92,65 @@ def given_tokens(model, b, given, given_unknown, device):
     return [int(v) for v in given_unknown], known.to(torch.uint8).contiguous(), fixed_tok
 
 
+def guidance_table(guidance_scale, Tmax, b, device=None):
+    """The guidance scales of a call as ONE fp32 table [Tmax, b] (row t: the scales of step t, one per video), contiguous, on `device`.
+    Accepted: a float (every step, every video); a sequence of Tmax floats (one per step, step 0 included); a tensor [b] (one per
+    video); a tensor [Tmax, b]."""
+    if torch.is_tensor(guidance_scale):
+        g = guidance_scale.detach().to(torch.float32)
+        if g.dim() == 0:
+            table = g.expand(Tmax, b)
+        elif tuple(g.shape) == (Tmax, b):
+            table = g
+        elif tuple(g.shape) == (b, ):
+            table = g.view(1, b).expand(Tmax, b)
+        else:
+            raise ValueError(f'guidance_scale: a tensor must be [b] = [{b}] (one scale per video) or [Tmax, b] = [{Tmax}, {b}], got '
+                             f'{tuple(g.shape)}')
+    elif isinstance(guidance_scale, (list, tuple, np.ndarray)):
+        vals = [float(v) for v in guidance_scale]
+        if len(vals) != Tmax:
+            raise ValueError(f'guidance_scale: a sequence holds one scale per step, step 0 included: {Tmax} values, got {len(vals)}')
+        table = torch.tensor(vals, dtype=torch.float32).view(Tmax, 1).expand(Tmax, b)
+    else:
+        try:
+            w = float(guidance_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'guidance_scale: expected a float, {Tmax} floats, a tensor [{b}] or a tensor [{Tmax}, {b}]; got '
+                             f'{type(guidance_scale).__name__}') from None
+        table = torch.full((Tmax, b), w, dtype=torch.float32)
+    if not table.is_cuda and not bool(torch.isfinite(table).all()):  # (a table already on the device is not read back)
+        raise ValueError('guidance_scale: every scale must be finite')
+    return table.to(device if device is not None else table.device).contiguous()
+
+
+GUIDANCE_DROPS = ('text', 'visual')
+
+
+def check_guidance(num_visuals, fixed_language_model, guidance_scale, guidance_drop, negative_text):
+    """The argument rules of generate_images' guidance keywords, before any device work -> the drop as a tuple, or None when the call
+    is unguided."""
+    if guidance_scale is None:
+        if negative_text is not None:
+            raise ValueError('negative_text without guidance_scale: a negative prompt acts only through the guided step')
+        return None
+    drop = (guidance_drop, ) if isinstance(guidance_drop, str) else tuple(guidance_drop)
+    unknown = [d for d in drop if d not in GUIDANCE_DROPS]
+    if unknown:
+        raise ValueError(f'guidance_drop: {unknown} is not among {GUIDANCE_DROPS}')
+    if 'visual' in drop and num_visuals == 0:
+        raise ValueError("guidance_drop names 'visual' on a model without a visual control (num_visuals == 0): pass guidance_drop=('text',)")
+    if not drop and negative_text is None:
+        raise ValueError('an empty guidance_drop without negative_text: the unconditional control would be the conditional one')
+    if 'text' in drop and fixed_language_model and negative_text is None:
+        raise ValueError("guidance_drop names 'text' on a model with a fixed language model: there is no defined null sentence "
+                         'feature; pass negative_text (the feature of a negative prompt) or drop only the visual control')
+    return drop
+
+
 @torch.no_grad()
 def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1, mp_config=None,
-                 long_mode='long', race=None, trace=None, given=None, given_unknown=None):
+                 long_mode='long', race=None, trace=None, given=None, given_unknown=None, uncond_emb=None, guidance_scale=None):
     """-> (tokens [b, TS] int64, image_samples list).  `race(name, shape)` supplies the Exp(1) variates (default: the
     device generator); `trace` (a list) receives one dict of the step's tensors per step (tests).
 
@@ -98,7 +158,16 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
     value from step 0 on, are visible to the tower in every candidate and are never re-masked; row i runs the schedule of its own
     N_i = TS - sum(mask[i]) unknown positions (keep count of step t: N_i - n_i[t - 1], read by the kernel from one device table built
     before the loop).  A row with nothing unknown returns its tokens, a row with nothing given is the plain sampler's.  Exclusive
-    with `preserve` and the interp modes, which are the two shared patterns of this.  See given_tokens for the one host read."""
+    with `preserve` and the interp modes, which are the two shared patterns of this.  See given_tokens for the one host read.
+
+    `uncond_emb` [b, csl, E] with `guidance_scale` (see guidance_table) switches classifier-free guidance on: every tower input is
+    built a second time from the same tokens and mask under `uncond_emb` and goes through the tower in a pass of its own, and tokens
+    and confidences come from lc + w * (lc - lu), w the scale of the step and of the row's video, read by the kernel from one device
+    table built before the loop.  The unconditional branch draws nothing and scores nothing.  With both None this is the unguided
+    code path, launch for launch."""
+    if (uncond_emb is None) != (guidance_scale is None):
+        raise ValueError('mask_predict: uncond_emb and guidance_scale come together (both, or neither)')
+    guided = uncond_emb is not None
     dev = control_emb.device
     b, csl, E = control_emb.shape
     TS, MASK, V = model.target_seq_len, model.image_token_lut['[MASK]'], model.num_image_tokens
@@ -120,16 +189,28 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
         k_table = torch.from_numpy(keep_table(mp_config, unknown, Tmax)).to(dev)
         keep_count = lambda t: k_table[t - 1]  # noqa: E731
 
+    if guided:
+        if tuple(uncond_emb.shape) != (b, csl, E):
+            raise ValueError(f'uncond_emb: expected the shape of control_emb {(b, csl, E)}, got {tuple(uncond_emb.shape)}')
+        scale = guidance_table(guidance_scale, Tmax, b, dev)
+
     control_emb = ops._chk(control_emb.contiguous().float(), torch.float32, 'control_emb')
+    if guided:
+        uncond_emb = ops._chk(uncond_emb.contiguous().float(), torch.float32, 'uncond_emb')
     iemb = model.image_emb.weight.detach()
     tpos = model.target_pos_emb.table().detach().contiguous()
     rel_head, vid_head = model.to_logits_rel, model.to_logits_vid
 
-    def tower_logits(I_in, mask1, nb):
-        x = ops.mp_build_input(control_emb, iemb, tpos, I_in, mask1, nb, MASK)
+    def tower_logits(I_in, mask1, nb, control=None):
+        x = ops.mp_build_input(control_emb if control is None else control, iemb, tpos, I_in, mask1, nb, MASK)
         out = model.transformer_forward(x)  # [b*nb, L, E]
         rows = out[:, csl:, :].reshape(b * nb * TS, E)
         return out, model.to_logits_rows(rows)
+
+    def draw_tokens(logits, logits_u, t, nb, Et, noise_u):
+        if not guided:
+            return ops.sample_race(logits, Et, noise_u, temp[t])
+        return ops.sample_race_guided(logits, logits_u, scale[t], nb * TS, Et, noise_u, temp[t])
 
     def noise(name, t, shape):
         if temp[t] == 0.0:
@@ -138,8 +219,9 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
 
     # ---- step 0: everything that is not given is [MASK]
     out, logits = tower_logits(fixed_tok, None, 1)
+    logits_u = tower_logits(fixed_tok, None, 1, uncond_emb)[1] if guided else None
     E0 = draw('tok0', (b * TS, V))
-    I_new, Y = ops.sample_race(logits, E0, noise('tok0', 0, (b * TS, V)), temp[0])
+    I_new, Y = draw_tokens(logits, logits_u, 0, 1, E0, noise('tok0', 0, (b * TS, V)))
     Y = Y.view(b, TS)
     I_tok = I_new.view(b, TS)
     if fixed is not None:
@@ -147,6 +229,8 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
     I_tok = I_tok.contiguous()
     if trace is not None:
         trace.append(dict(t=0, logits=logits, E_tok=E0, Y=Y.clone(), I_tok=I_tok.clone()))
+        if guided:
+            trace[-1].update(logits_u=logits_u, scale=scale[0])
     Imax = I_tok.clone()
     Smax = torch.zeros(b, device=dev)
     tmax = torch.zeros(b, dtype=torch.int32, device=dev)
@@ -160,8 +244,9 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
         Ek = draw(f'keep{t}', (b, Bm, TS))
         mask1 = ops.mp_select_keep(Y, Ek, fixed, keep_count(t))
         out, logits = tower_logits(I_tok, mask1, Bm)
+        logits_u = tower_logits(I_tok, mask1, Bm, uncond_emb)[1] if guided else None
         Et = draw(f'tok{t}', (b * Bm * TS, V))
-        Inew, Ynew = ops.sample_race(logits, Et, noise(f'tok{t}', t, (b * Bm * TS, V)), temp[t])
+        Inew, Ynew = draw_tokens(logits, logits_u, t, Bm, Et, noise(f'tok{t}', t, (b * Bm * TS, V)))
         out2d = out.view(b * Bm * L, E)
         z_rel = ops.head_rows_fwd(out2d, rel_rows, rel_head[0].weight, rel_head[0].bias, rel_head[1].weight.view(-1),
                                   rel_head[1].bias, rel_head[0].eps)[0]
@@ -173,6 +258,8 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
                        Inew=Inew.view(b, Bm, TS), z_rel=z_rel, z_vid=z_vid, Y_before=Y.clone(), I_before=I_tok.clone(),
                        active_before=active.clone(), S=torch.empty(b, Bm, device=dev),
                        jmax=torch.empty(b, dtype=torch.int32, device=dev))
+            if guided:
+                rec.update(logits_u=logits_u, scale=scale[t])
         ops.mp_update(mask1, Ynew, Inew, z_rel, z_vid, t, dynamic, Y, I_tok, Imax, Smax, tmax, active,
                       rec['S'] if rec else None, rec['jmax'] if rec else None)
         if rec is not None and trace is not None:
