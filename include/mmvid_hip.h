@@ -486,6 +486,17 @@ int mmvid_sample_race_at(const float* logits, int64_t ld, const float* E, const 
 int mmvid_sample_race_guided(const float* logits_c, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
                              const float* E, const float* noise_u, float temperature, float logit_div, int64_t R, int V,
                              int64_t tok_offset, int64_t* tok, float* y, void* stream);
+/* Top-k and nucleus (top-p) truncation of the logits both samplers draw from (dalle_bert.py:527-534: BERT draws from the full softmax;
+ * dalle_artv.py:61-67,274-276: ART-V's top_k filter), on the device.  Per row r: g_c = logits[r][c], or with logits_u != NULL the
+ * guided value of mmvid_sample_race_guided (same ld, scale_dev [R / rows_per_scale], R % rows_per_scale == 0).  The classes are
+ * ordered by g descending, ties to the lower index, -0.0 == +0.0.  P_c = expf(g_c / logit_div - max), S = sum P, M_before(c) = the
+ * mass of the classes ordered before c.  top_k in [1, V) keeps the first top_k classes of the order (anything else: off); top_p in
+ * (0, 1) keeps c iff M_before(c) < top_p * S (top_p >= 1: off); with both a class must pass both.  out[r][c] = g_c where kept,
+ * -inf elsewhere (row stride ld_out; out == logits with ld_out == ld is allowed when logits_u == NULL); kept (may be NULL) int32 [R]:
+ * the number of finite outputs.  mmvid_sample_race(out, ..., logit_div) is then the truncated draw.  1 <= V <= 2048.  No atomics. */
+int mmvid_logits_truncate(const float* logits, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
+                          float logit_div, int top_k, float top_p, int64_t R, int V,
+                          float* out, int64_t ld_out, int32_t* kept, void* stream);
 /* keep-mask of a refinement step (dalle_bert.py:646-668): of the positions with preserve == 0, the k with the smallest
  * E / Y stay visible (k outside [1, #non-zero weights] -> 1, the reference's except branch); preserved positions always
  * stay.  Y [b, TS], E [b, Bm, TS], mask1 out [b, Bm, TS] (1 = keep). */

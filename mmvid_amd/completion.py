@@ -62,14 +62,14 @@ def _frames_to_tokens(model, frames, b):
 @torch.no_grad()
 def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, mp_config=None, dynamic=True, erase_visual=False,
              vc_mode=None, face_mode=None, decode=True, paste=True, guidance_scale=None, guidance_drop=('text', 'visual'),
-             negative_text=None, _race=None, _trace=None):
+             negative_text=None, top_k=None, top_p=None, _race=None, _trace=None):
     """Complete `b` videos of `num_targets` frames -> (frames_u8 [b, T, H, W, 3] uint8 on the device, or None without `decode`;
     tokens [b, T, n] int64).
 
     `frames`: the videos as fp32 [b, T, 3, H, W] in [0, 1], uint8 [b, T, H, W, 3], or int64 tokens [b, T * n]; only what `given`
     marks is read as known.  Pixels are tokenised by `model.get_image_tokens` in the VQGAN's current `strict` mode; 'split' is the
     mode whose indices are exact.  `given`: see token_mask; every video may have its own.  `text`, `visual`, `erase_visual`,
-    `vc_mode`, `face_mode`, `mask_predict_steps`, `mp_config`, `dynamic`, `guidance_scale`, `guidance_drop`, `negative_text`: as for
+    `vc_mode`, `face_mode`, `mask_predict_steps`, `mp_config`, `dynamic`, `guidance_scale`, `guidance_drop`, `negative_text`, `top_k`, `top_p`: as for
     generate_images (guided completion: the given tokens are visible to both branches, and belong to the conditional one).
 
     One host read precedes the sampler's loop: the number of known tokens per video together with the count of given token ids
@@ -82,6 +82,8 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
     if guidance_scale is not None or negative_text is not None:
         drop = sampling.check_guidance(model.num_visuals, model.fixed_language_model is not None, guidance_scale, guidance_drop,
                                        negative_text)
+    if top_k is not None or top_p is not None:
+        sampling.check_truncation(top_k, top_p, mp_config['T'] if mask_predict_steps <= 0 else mask_predict_steps, model.num_image_tokens)
     T, n, s, f = model.num_targets, model.image_seq_len, model.image_size, model.image_fmap_size
     b, dev = text.shape[0], text.device
     V = model.num_image_tokens
@@ -109,7 +111,7 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
                 text, drop, negative_text, visual=visual, erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode))
         mask, tokens = mask.to(dev), tokens.to(dev)
         seq = model.mask_predict(control, dynamic=dynamic, steps=mask_predict_steps, mp_config=mp_config, given=(mask, tokens),
-                                 _given_unknown=unknown, _race=_race, _trace=_trace, **guide)[0]
+                                 _given_unknown=unknown, _race=_race, _trace=_trace, top_k=top_k, top_p=top_p, **guide)[0]
         out = None
         if decode:
             flat = seq.view(b * T, n)

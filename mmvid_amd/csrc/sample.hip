@@ -9,6 +9,17 @@
 // so the host fills E with torch's exponential_() in production and the tests inject the same E into oracle/sampling.py
 // and require identical decisions.  E / P is one correctly-rounded fp32 division on both sides.
 // All kernels are HBM/latency-bound row kernels: one wave per row, coalesced 4-B/16-B accesses.
+//
+// Truncation rule (logits_truncate_kernel: top-k and nucleus, for both samplers).  Per row, g_c is the value that enters the race
+// (the logit, or guided_logit of the two branches).  The classes are ordered by g descending, ties to the lower index, -0.0 == +0.0;
+// rank(c) is the position in that order.  P_c = expf(g_c * (1 / logit_div) - max), S = sum P, M_before(c) = sum of P_j over
+// rank(j) < rank(c).
+//   top-k   (1 <= top_k < V, anything else: off)          keep rank(c) < top_k: exactly top_k classes
+//   top-p   (0 < top_p < 1; top_p >= 1: off, no mass test)  keep c iff M_before(c) < top_p * S: rank 0 always, and the smallest
+//                                                          head of the order whose mass reaches top_p
+// With both on a class must pass both.  out = g where kept (not divided), -inf elsewhere; kept[r] = number of finite outputs.  So
+// sample_race(out, E, noise_u, temperature, logit_div) is the truncated draw, its y the probability under the truncated distribution,
+// and noise never brings an excluded class back.
 #include "../../include/mmvid_hip.h"
 #include "common.h"
 
@@ -140,6 +151,115 @@ __global__ __launch_bounds__(256) void sample_race_row_kernel(const float* __res
         b = better(better(sb[0], sb[1]), better(sb[2], sb[3]));
         tok_out[r] = (long long)(b.idx < V ? b.idx : 0) + tok_offset;
     }
+}
+
+// ---- top-k / nucleus truncation (the rule is in the header comment).  One wave per row, the row in registers: class lane + 64 i is
+// slot i of its lane, NS = ceil(V / 64) rounded up to 4, 16 or 32 slots.  Both edges are found by a 32-step bitwise search over the
+// order-preserving key of g (larger value = larger key):
+//   top-k  T = the largest key with  #(key >= T) >= top_k              counts: ballots and scalar popcounts
+//   top-p  T = the largest key with  mass(key >= T) >= top_p * S       masses: every lane adds its slots in slot order, then one
+//                                                                      butterfly; S is the same sum with nothing left out
+// fp32 addition of non-negative terms in a fixed order never decreases when a term joins, so both predicates are monotone in T and
+// each search ends on a key that is present.  Classes above the edge key stay; of the classes AT it, the first few in index order
+// (class lane + 64 i comes after every slot < i and after the lower lanes of slot i: popcounts of the earlier ballots plus the
+// ballot of slot i under the lanes-below mask): top-k admits top_k - #(key > T) of them, top-p the j-th (j = 0, 1, ...) while
+// mass(key > T) + j * P < top_p * S.  Every loop has a fixed trip count; no LDS, no barrier, nothing but the row's own stores, which
+// follow all of its loads (out may be logits).
+__device__ __forceinline__ uint32_t order_key(float v) {
+    const uint32_t u = v == 0.f ? 0u : __float_as_uint(v);  // -0.0 and +0.0 are one value
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float first_lane(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+
+template <int NS, bool GUIDED>
+__global__ __launch_bounds__(256) void logits_truncate_kernel(const float* logits, const float* logits_u, long ld,
+                                                              const float* __restrict__ scale_dev, long rows_per_scale, float inv_div,
+                                                              int top_k, float top_p, long R, int V, float* out, long ld_out,
+                                                              int* __restrict__ kept) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const float* x = logits + r * ld;
+    const float* xu = GUIDED ? logits_u + r * ld : nullptr;
+    const float w = GUIDED ? scale_dev[r / rows_per_scale] : 0.f;
+    float g[NS], p[NS];
+    uint32_t key[NS];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int c = lane + 64 * i;
+        const bool on = c < V;
+        g[i] = on ? (GUIDED ? guided_logit(x[c], xu[c], w) : x[c]) : -INFINITY;
+        key[i] = on ? order_key(g[i]) : 0u;  // below the key of every value, -inf included: a slot past V is never counted
+        mx = fmaxf(mx, g[i] * inv_div);
+    }
+    mx = wave_max(mx);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) p[i] = mx == -INFINITY ? 0.f : expf(g[i] * inv_div - mx);  // (a row of -inf has no mass; a slot past V: expf(-inf))
+    uint32_t keep = 0xffffffffu;  // bit i: slot i stays
+    if (top_k >= 1 && top_k < V) {
+        uint32_t T = 0;
+#pragma unroll 1
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = T | (1u << bit);
+            int n = 0;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) n += __popcll(__ballot(key[i] >= cand));
+            if (n >= top_k) T = cand;
+        }
+        int above = 0;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) above += __popcll(__ballot(key[i] > T));
+        const int quota = top_k - above;
+        int before = 0;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const bool at = key[i] == T;
+            const unsigned long long b = __ballot(at);
+            const int j = before + __popcll(b & below);
+            before += __popcll(b);
+            if (!(key[i] > T || (at && j < quota))) keep &= ~(1u << i);
+        }
+    }
+    if (top_p < 1.f) {
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) s += p[i];
+        const float theta = top_p * first_lane(wave_sum_fast(s));
+        uint32_t T = 0;
+#pragma unroll 1
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = T | (1u << bit);
+            float m = 0.f;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) m += key[i] >= cand ? p[i] : 0.f;
+            if (first_lane(wave_sum_fast(m)) >= theta) T = cand;
+        }
+        float m = 0.f;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) m += key[i] > T ? p[i] : 0.f;
+        const float m_above = first_lane(wave_sum_fast(m));
+        int before = 0;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            const bool at = key[i] == T;
+            const unsigned long long b = __ballot(at);
+            const int j = before + __popcll(b & below);
+            before += __popcll(b);
+            if (!(key[i] > T || (at && m_above + (float)j * p[i] < theta))) keep &= ~(1u << i);
+        }
+    }
+    float* o = out + r * ld_out;
+    int n_kept = 0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int c = lane + 64 * i;
+        const bool k = c < V && ((keep >> i) & 1u);
+        if (c < V) o[c] = k ? g[i] : -INFINITY;
+        n_kept += __popcll(__ballot(k && fabsf(g[i]) < INFINITY));
+    }
+    if (kept && lane == 0) kept[r] = n_kept;
 }
 
 // grid (Bm, b); dynamic LDS: TS floats.  `preserve` is read with a row stride: 0 = one [TS] mask shared by every video (or null:
@@ -530,6 +650,48 @@ extern "C" int mmvid_sample_race_guided(const float* logits_c, const float* logi
                        scale_dev, (long)rows_per_scale, E, noise_u, temperature, 1.0f / logit_div, (long)R, V, (long long)tok_offset,
                        (long long*)tok, y);
     MMVID_LAUNCH_CHECK("sample_race_guided");
+    return MMVID_OK;
+}
+
+// Top-k / nucleus truncation of R rows (the rule: header comment).  logits_u == null: g = logits; otherwise g = guided_logit of the two
+// tensors (one ld) with w = scale_dev[r / rows_per_scale].  out [R, V] with its own ld_out; out == logits with ld_out == ld is allowed
+// in the unguided form.  kept (nullable) int32 [R].  Both filters off: the rows are copied through.
+template <bool GUIDED>
+static void launch_logits_truncate(const float* logits, const float* logits_u, long ld, const float* scale_dev, long rows_per_scale,
+                                   float inv_div, int top_k, float top_p, long R, int V, float* out, long ld_out, int* kept,
+                                   hipStream_t stream) {
+    const dim3 grid(cdiv(R, 4)), block(256);
+    if (V <= 256)
+        hipLaunchKernelGGL((logits_truncate_kernel<4, GUIDED>), grid, block, 0, stream, logits, logits_u, ld, scale_dev, rows_per_scale,
+                           inv_div, top_k, top_p, R, V, out, ld_out, kept);
+    else if (V <= 1024)
+        hipLaunchKernelGGL((logits_truncate_kernel<16, GUIDED>), grid, block, 0, stream, logits, logits_u, ld, scale_dev, rows_per_scale,
+                           inv_div, top_k, top_p, R, V, out, ld_out, kept);
+    else
+        hipLaunchKernelGGL((logits_truncate_kernel<32, GUIDED>), grid, block, 0, stream, logits, logits_u, ld, scale_dev, rows_per_scale,
+                           inv_div, top_k, top_p, R, V, out, ld_out, kept);
+}
+
+extern "C" int mmvid_logits_truncate(const float* logits, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
+                                     float logit_div, int top_k, float top_p, int64_t R, int V, float* out, int64_t ld_out, int32_t* kept,
+                                     void* stream) {
+    MMVID_REQUIRE(logits && out, "logits_truncate: null logits or out");
+    MMVID_REQUIRE(V >= 1 && V <= 2048, "logits_truncate: V=%d is outside [1, 2048] (a wave holds its row in registers)", V);
+    MMVID_REQUIRE(R >= 0 && ld >= V && ld_out >= V, "logits_truncate: R=%ld ld=%ld ld_out=%ld V=%d", (long)R, (long)ld, (long)ld_out, V);
+    MMVID_REQUIRE(logit_div > 0.f, "logits_truncate: logit_div (the softmax temperature divisor) must be > 0");
+    MMVID_REQUIRE(top_p > 0.f, "logits_truncate: top_p must be > 0 (>= 1 switches the nucleus off)");  // (false for NaN too)
+    MMVID_REQUIRE((logits_u != nullptr) == (scale_dev != nullptr), "logits_truncate: logits_u and scale_dev come together (the guided form)");
+    if (logits_u)
+        MMVID_REQUIRE(rows_per_scale > 0 && R % rows_per_scale == 0, "logits_truncate: R=%ld is no multiple of rows_per_scale=%ld", (long)R,
+                      (long)rows_per_scale);
+    if (R == 0) return MMVID_OK;
+    if (logits_u)
+        launch_logits_truncate<true>(logits, logits_u, (long)ld, scale_dev, (long)rows_per_scale, 1.0f / logit_div, top_k, top_p, (long)R, V,
+                                     out, (long)ld_out, (int*)kept, (hipStream_t)stream);
+    else
+        launch_logits_truncate<false>(logits, nullptr, (long)ld, nullptr, 1L, 1.0f / logit_div, top_k, top_p, (long)R, V, out, (long)ld_out,
+                                      (int*)kept, (hipStream_t)stream);
+    MMVID_LAUNCH_CHECK("logits_truncate");
     return MMVID_OK;
 }
 

@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, ops, sampling
 from .clip_tower import OpenAICLIPTransformer
 from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
 from .frontend import Frontend, face_choices
@@ -275,7 +275,16 @@ class DALLE(nn.Module):
                                      self._seg[first_pos:first_pos + n].contiguous(),
                                      self._pos_rows()[first_pos:first_pos + n].contiguous())
 
-    def _draw(self, block_logits, filter_thres, temperature, race, name):
+    def _truncation(self, top_k, top_p, V):
+        """generate_images' `top_k` / `top_p` (scalars; sampling.check_truncation, before any device work) -> (k | None, p | None), or
+        None when neither can remove a class of the V-class image block."""
+        trunc = sampling.check_truncation(top_k, top_p, 1, V)
+        if trunc is None:
+            return None
+        k, p = trunc[0][0], trunc[1][0]
+        return (k, p) if (k is not None and k < V) or (p is not None and p < 1.0) else None
+
+    def _draw(self, block_logits, filter_thres, temperature, race, name, trunc=None):
         """One token per row from the logits of the position's class block (dalle_artv.py:274-276): top_k over ALL
         total_tokens classes keeps k = int((1 - thres) * total_tokens) of them; the classes outside the block sit at -max,
         so the filter only ever removes block classes when k is smaller than the block."""
@@ -285,16 +294,20 @@ class DALLE(nn.Module):
             kept = torch.full_like(block_logits, float('-inf'))
             val, ind = torch.topk(block_logits, k_keep)
             block_logits = kept.scatter_(1, ind, val)
+        block_logits = block_logits.contiguous()
+        if trunc is not None:  # top-k / nucleus of what filter_thres left (ops.logits_truncate)
+            block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logit_div=temperature)
         E = race(name, (B, n)) if race is not None else ops.exponential_like((B, n), block_logits.device)
-        tok, _ = ops.sample_race(block_logits.contiguous(), E, None, 0.0, logit_div=temperature, want_y=False)
+        tok, _ = ops.sample_race(block_logits, E, None, 0.0, logit_div=temperature, want_y=False)
         return tok.view(B, 1)
 
-    def _sample_cached(self, h, cache, first_pos, filter_thres, temperature, race):
+    def _sample_cached(self, h, cache, first_pos, filter_thres, temperature, race, trunc=None):
         """The sampling loop over the key/value cache.  One token = [head logits of the image block -> draw -> embedding
         row of the drawn token -> one decode step through the tower]; that chain is captured once (hipGraph) and replayed
         per token: the position lives in a device scalar the step advances, the race variates come from torch's
-        graph-safe device generator.  Injected variates (`race`, tests) or a top-k that actually filters run the same
-        kernels eagerly."""
+        graph-safe device generator.  Injected variates (`race`, tests) or a `filter_thres` that actually filters run the same
+        kernels eagerly.  `trunc` = (top_k, top_p) adds ONE launch between the head and the draw (ops.logits_truncate, in place on
+        the logits the draw reads); it is captured with the rest and does not bear on `use_graph`."""
         B, dev = h.shape[0], h.device
         c0, c1 = self._allowed_range(self.control_seq_len)
         V = c1 - c0
@@ -326,6 +339,8 @@ class DALLE(nn.Module):
             if k_keep < V:
                 val, ind = torch.topk(lg, k_keep)
                 lg = torch.full_like(lg, float('-inf')).scatter_(1, ind, val)
+            if trunc is not None:
+                ops.logits_truncate(lg, trunc[0], trunc[1], logit_div=temperature, out=lg)
             if E_all is not None:
                 ops.sample_race(lg, E_all, None, 0.0, logit_div=temperature, want_y=False, tok_out=tok, step_dev=sess.pos, step0=first_pos)
                 return
@@ -348,7 +363,9 @@ class DALLE(nn.Module):
         # batch 1-2 in production: the whole token (embedding -> tower -> head -> draw) is ONE persistent launch (MMVID_DECODE_TOKEN=0: the
         # launches below).  The first token is drawn from the prompt's hidden state the usual way; every launch then embeds the token drawn
         # last, files it in `out`, and draws the next one.
-        if (use_graph and sess.persistent and E_all is not None and V <= 2048 and os.environ.get('MMVID_DECODE_TOKEN', '1') != '0'):
+        # (that launch has no truncation in it: a call with top_k / top_p takes the launches below)
+        if (use_graph and sess.persistent and E_all is not None and V <= 2048 and trunc is None and
+                os.environ.get('MMVID_DECODE_TOKEN', '1') != '0'):
             tk = _lib.DecodeToken()
             tk.tok, tk.table, tk.table_rows, tk.pos_rows, tk.pos_off = tok.data_ptr(), iemb.data_ptr(), iemb.shape[0], pos_rows.data_ptr(), 0
             tk.record, tk.record_ld, tk.record_pos0 = out.data_ptr(), out.stride(0), first_pos
@@ -425,22 +442,29 @@ class DALLE(nn.Module):
         sess.check()
         return [out[:, i:i + 1] for i in range(steps)]
 
-    def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0):
+    def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None):
         """The probability vector `_draw` samples from (tests compare it with the reference's full-width expression)."""
+        trunc = self._truncation(top_k, top_p, block_logits.shape[1])
         k_keep = max(int((1 - filter_thres) * self.total_tokens), 1)
         if k_keep < block_logits.shape[1]:
             val, ind = torch.topk(block_logits, k_keep)
             block_logits = torch.full_like(block_logits, float('-inf')).scatter_(1, ind, val)
+        if trunc is not None:
+            block_logits = ops.logits_truncate(block_logits.contiguous(), trunc[0], trunc[1], logit_div=temperature)
         return F.softmax(block_logits / temperature, dim=-1)
 
     @torch.no_grad()
     @eval_decorator
     def generate_images(self, text, *, clip=None, visual=None, mask=None, filter_thres=0.5, temperature=1.,
-                        erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, _race=None, **kwargs):
+                        erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, _race=None, **kwargs):
         """dalle_artv.py:236-304.  use_cache=True (default): the prompt runs once and every sampled token costs one
         incremental step over the per-layer key/value cache; use_cache=False: the reference's algorithm (the whole
         transformer over the growing prefix per token).  Both draw from the same distribution: softmax over the image
-        block of the last position's logits (tests/test_parity_gpu.py compares it with the reference's expression)."""
+        block of the last position's logits (tests/test_parity_gpu.py compares it with the reference's expression).
+        `top_k` (an int) / `top_p` (a float in (0, 1]) truncate that distribution, after whatever `filter_thres` did, to its k most
+        likely classes / to its nucleus of mass top_p, with defined ties (ops.logits_truncate): one more launch per token, captured
+        with the step."""
+        trunc = self._truncation(top_k, top_p, self.num_image_tokens)
         tsl = self.text_seq_len
         text = text[:, :tsl]
         B = text.shape[0]
@@ -454,13 +478,13 @@ class DALLE(nn.Module):
             cache = self.transformer.new_kv_cache(B, self.total_seq_len, text.device)
             prompt = torch.cat(self._prompt_ids(text, vis_tok), 1)  # <bos> text visual: positions 0 .. cl
             h = self.transformer.prefill(self._embed_rows(prompt, 0), cache)[:, -1, :].contiguous()
-            toks = self._sample_cached(h, cache, prompt.shape[1], filter_thres, temperature, _race)
+            toks = self._sample_cached(h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc)
         else:
             image = torch.empty(B, 0, dtype=torch.long, device=text.device)
             for step in range(self.target_seq_len):
                 hidden = self._hidden(text, vis_tok, image)[0]
                 sample = self._draw(self._logits_rows(hidden[:, -1, :].contiguous(), (c0, c1)), filter_thres, temperature,
-                                    _race, f'tok{step}')
+                                    _race, f'tok{step}', trunc)
                 toks.append(sample)
                 image = torch.cat((image, sample), dim=-1)
         img_seq = torch.cat(toks, dim=-1).reshape(-1, self.image_seq_len)

@@ -568,12 +568,17 @@ class BERT(nn.Module):
     def generate_images(self, text, *, visual=None, mask=None, img=None, argmax=False, dynamic=True, debug=False,
                         erase_visual=False, mask_predict_steps=10, preserve=None, t_overlap=1, pc_mode=None,
                         vc_mode=None, face_mode=None, mp_config=None, long_mode='long', guidance_scale=None,
-                        guidance_drop=('text', 'visual'), negative_text=None, **kwargs):
+                        guidance_drop=('text', 'visual'), negative_text=None, top_k=None, top_p=None, **kwargs):
         """dalle_bert.py:434-487 -> (images [b,T,3,H,W], pnag_samples, img_seq [(b T), n]).  `guidance_scale` (a float, one per step,
         one per video or [steps, b]: sampling.guidance_table) switches classifier-free guidance on; see guidance_control for
-        `guidance_drop` and `negative_text`."""
+        `guidance_drop` and `negative_text`.  `top_k` / `top_p` (an int / a float, or one per step: sampling.check_truncation) draw
+        every token from the k most likely classes / from the nucleus of mass top_p (of the guided distribution when guided)."""
         drop = sampling.check_guidance(self.num_visuals, self.fixed_language_model is not None, guidance_scale, guidance_drop,
                                        negative_text)
+        if top_k is not None or top_p is not None:
+            Tmax = (mp_config or {}).get('T', 0) if mask_predict_steps <= 0 else mask_predict_steps
+            sampling.check_truncation(top_k, top_p, Tmax, self.num_image_tokens)
+            kwargs.update(top_k=top_k, top_p=top_p)
         control_emb = self(text, visual=visual, erase_visual=erase_visual, erase_visual_half=True, vc_mode=vc_mode,
                            face_mode=face_mode, return_loss=False)
         if drop is not None:
@@ -604,10 +609,11 @@ class BERT(nn.Module):
     @torch.no_grad()
     def mask_predict(self, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1,
                      mp_config=None, long_mode='long', _race=None, _trace=None, given=None, _given_unknown=None, uncond_emb=None,
-                     guidance_scale=None, **kwargs):
+                     guidance_scale=None, top_k=None, top_p=None, **kwargs):
         """dalle_bert.py:514-714, batched over videos and beam candidates on the device (mmvid_amd/sampling.py).  `given` = (mask
         [b, TS], tokens [b, TS]): per-video known tokens (mmvid_amd/completion.py).  `uncond_emb` [b, csl, E] with `guidance_scale`:
-        classifier-free guidance (sampling.mask_predict)."""
+        classifier-free guidance; `top_k`, `top_p`: truncated sampling (both: sampling.mask_predict)."""
         return sampling.mask_predict(self, control_emb, dynamic=dynamic, debug=debug, steps=steps, preserve=preserve,
                                      t_overlap=t_overlap, mp_config=mp_config, long_mode=long_mode, race=_race, trace=_trace,
-                                     given=given, given_unknown=_given_unknown, uncond_emb=uncond_emb, guidance_scale=guidance_scale)
+                                     given=given, given_unknown=_given_unknown, uncond_emb=uncond_emb, guidance_scale=guidance_scale,
+                                     top_k=top_k, top_p=top_p)

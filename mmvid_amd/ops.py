@@ -643,6 +643,47 @@ def sample_race_guided(logits_c, logits_u, scale, rows_per_scale, E, noise_u=Non
     return tok, y
 
 
+def logits_truncate(logits, top_k=None, top_p=None, *, logits_u=None, scale=None, rows_per_scale=None, logit_div=1.0, out=None,
+                    want_kept=False):
+    """Top-k / nucleus truncation of logits [R, V] f32 (row stride = logits.stride(0), V <= 2048) -> out [R, V] (`out` if given; it may
+    be `logits` itself; the header promises that for the unguided form, and the guided one is as safe: a wave holds its row of
+    both tensors before it stores), or (out, kept int32 [R]: the finite entries per row) with want_kept.  Classes by value
+    descending, ties to the lower index: top_k (1 <= top_k < V, else off) keeps the first top_k; top_p (< 1, else off) keeps a class
+    iff the mass before it, of P = exp(g / logit_div - max), is below top_p * sum P.  Kept entries hold their value (not divided),
+    the others -inf, so sample_race(out, E, noise_u, temperature, logit_div) is the truncated draw.  With logits_u, scale f32
+    [R // rows_per_scale] and rows_per_scale the value truncated (and written) is lc + w * (lc - lu) as sample_race_guided reads it."""
+    def rows(t, name, shape=None):  # _chk for a tensor that may be a column window of a wider one (a row stride of its own)
+        _chk(t[:1], f32, name)
+        if t.dim() != 2 or t.stride(1) != 1 or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f'logits_truncate: {name} must be f32 {shape or "[R, V]"} with unit column stride, got {tuple(t.shape)}')
+
+    rows(logits, 'logits')
+    R, V = logits.shape
+    k = 0 if top_k is None else min(int(top_k), V)  # (top_k >= V is off: no huge value reaches the C int)
+    p = 1.0 if top_p is None else float(top_p)
+    if (logits_u is None) != (scale is None) or (logits_u is None) != (rows_per_scale is None):
+        raise ValueError('logits_truncate: logits_u, scale and rows_per_scale come together (the guided form)')
+    if logits_u is not None:
+        rows(logits_u, 'logits_u', (R, V)), _chk(scale, f32, 'scale')
+        if logits_u.stride(0) != logits.stride(0):
+            raise ValueError(f'logits_truncate: logits_u (row stride {logits_u.stride(0)}) must have the row stride of logits '
+                             f'({logits.stride(0)})')
+        rows_per_scale = int(rows_per_scale)
+        if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
+            raise ValueError(f'logits_truncate: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
+    if out is None:
+        out = torch.empty(R, V, device=logits.device, dtype=f32)
+    else:
+        rows(out, 'out', (R, V))
+    kept = torch.empty(R, device=logits.device, dtype=torch.int32) if want_kept else None
+    if R == 0:  # (an empty tensor has no address to pass)
+        return (out, kept) if want_kept else out
+    call('mmvid_logits_truncate', _p(logits), _p(logits_u), logits.stride(0) if R > 1 else V, _p(scale),
+         rows_per_scale if logits_u is not None else 1, float(logit_div), k, p, R, V, _p(out), out.stride(0) if R > 1 else V, _p(kept),
+         _stream())
+    return (out, kept) if want_kept else out
+
+
 def mp_select_keep(Y, E, preserve, k):
     """Y [b, TS], E [b, Bm, TS], preserve [TS] uint8 or None -> mask1 [b, Bm, TS] uint8 (1 = position stays visible).
     A 2-D preserve [b, TS] with a tensor k (int32 [b] on the device) is the per-video form: row i has its own mask and keep count."""

@@ -148,9 +148,43 @@ def check_guidance(num_visuals, fixed_language_model, guidance_scale, guidance_d
     return drop
 
 
+def check_truncation(top_k, top_p, Tmax, V):
+    """The argument rules of the samplers' truncation keywords, before any device work -> (k per step, p per step): two host lists of
+    Tmax entries (None = that filter is off at that step), or None when both keywords are None.  Accepted: an int / a float (every
+    step), or a sequence of Tmax of them, one per step, step 0 included, whose None entries switch the filter off for the step.  The
+    values are baked into the launches: a tensor (a per-video form) is refused.  A top_k >= V keeps every class."""
+    if top_k is None and top_p is None:
+        return None
+
+    def per_step(value, name, one):
+        if value is None:
+            return [None] * Tmax
+        if torch.is_tensor(value):
+            raise ValueError(f'{name}: a tensor is not accepted (the value is a launch argument; there is no per-video form)')
+        if isinstance(value, (list, tuple, np.ndarray)):
+            vals = list(value)
+            if len(vals) != Tmax:
+                raise ValueError(f'{name}: a sequence holds one value per step, step 0 included: {Tmax} values, got {len(vals)}')
+            return [None if v is None else one(v) for v in vals]
+        return [one(value)] * Tmax
+
+    def one_k(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f'top_k: expected an integer >= 1 (or None: off), got {v!r}')
+        return int(v)
+
+    def one_p(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) <= 1.0:
+            raise ValueError(f'top_p: expected a finite float in (0, 1] (or None: off), got {v!r}')
+        return float(v)
+
+    return per_step(top_k, 'top_k', one_k), per_step(top_p, 'top_p', one_p)
+
+
 @torch.no_grad()
 def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1, mp_config=None,
-                 long_mode='long', race=None, trace=None, given=None, given_unknown=None, uncond_emb=None, guidance_scale=None):
+                 long_mode='long', race=None, trace=None, given=None, given_unknown=None, uncond_emb=None, guidance_scale=None,
+                 top_k=None, top_p=None):
     """-> (tokens [b, TS] int64, image_samples list).  `race(name, shape)` supplies the Exp(1) variates (default: the
     device generator); `trace` (a list) receives one dict of the step's tensors per step (tests).
 
@@ -164,7 +198,11 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
     built a second time from the same tokens and mask under `uncond_emb` and goes through the tower in a pass of its own, and tokens
     and confidences come from lc + w * (lc - lu), w the scale of the step and of the row's video, read by the kernel from one device
     table built before the loop.  The unconditional branch draws nothing and scores nothing.  With both None this is the unguided
-    code path, launch for launch."""
+    code path, launch for launch.
+
+    `top_k`, `top_p` (see check_truncation): at a step with a filter on, the logits (the guided value when guided) first go through
+    ops.logits_truncate and the plain race then draws from what is left, so `Y` is the confidence under the truncated distribution.
+    A step with both off, and a call with both None, is the code path without them."""
     if (uncond_emb is None) != (guidance_scale is None):
         raise ValueError('mask_predict: uncond_emb and guidance_scale come together (both, or neither)')
     guided = uncond_emb is not None
@@ -177,6 +215,9 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
     Bm = mp_config['B']
     if Tmax < 2:
         raise RuntimeError('mask_predict needs at least 2 steps (the reference returns nothing for steps == 1)')
+    trunc = check_truncation(top_k, top_p, Tmax, V)
+    # the steps at which a filter can remove a class; at the others (k >= V, p = 1, None) the draw is the one without the keywords
+    trunc_on = [False] * Tmax if trunc is None else [(k is not None and k < V) or (p is not None and p < 1.0) for k, p in zip(*trunc)]
     if given is None:
         N, fixed, fixed_tok = preserved_tokens(model, b, preserve, t_overlap, long_mode, dev)
         n, temp = schedule(mp_config, N)
@@ -207,7 +248,17 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
         rows = out[:, csl:, :].reshape(b * nb * TS, E)
         return out, model.to_logits_rows(rows)
 
+    truncated = {}  # what the truncated draw of the current step read: {'logits_t', 'kept'} (the trace keeps it)
+
     def draw_tokens(logits, logits_u, t, nb, Et, noise_u):
+        truncated.clear()
+        if trunc_on[t]:
+            guide = dict(logits_u=logits_u, scale=scale[t], rows_per_scale=nb * TS) if guided else {}
+            lg = ops.logits_truncate(logits, trunc[0][t], trunc[1][t], want_kept=trace is not None, **guide)
+            if trace is not None:
+                truncated.update(logits_t=lg[0], kept=lg[1])
+                lg = lg[0]
+            return ops.sample_race(lg, Et, noise_u, temp[t])
         if not guided:
             return ops.sample_race(logits, Et, noise_u, temp[t])
         return ops.sample_race_guided(logits, logits_u, scale[t], nb * TS, Et, noise_u, temp[t])
@@ -231,6 +282,7 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
         trace.append(dict(t=0, logits=logits, E_tok=E0, Y=Y.clone(), I_tok=I_tok.clone()))
         if guided:
             trace[-1].update(logits_u=logits_u, scale=scale[0])
+        trace[-1].update(truncated)
     Imax = I_tok.clone()
     Smax = torch.zeros(b, device=dev)
     tmax = torch.zeros(b, dtype=torch.int32, device=dev)
@@ -260,6 +312,7 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
                        jmax=torch.empty(b, dtype=torch.int32, device=dev))
             if guided:
                 rec.update(logits_u=logits_u, scale=scale[t])
+            rec.update(truncated)
         ops.mp_update(mask1, Ynew, Inew, z_rel, z_vid, t, dynamic, Y, I_tok, Imax, Smax, tmax, active,
                       rec['S'] if rec else None, rec['jmax'] if rec else None)
         if rec is not None and trace is not None:

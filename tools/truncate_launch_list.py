@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""The calls of both samplers WITHOUT the truncation keywords, on the tiny models of the tests, for a kernel-trace run: the kernel list of
+this tree must be the parent commit's (no launch added, none changed).
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python tools/truncate_launch_list.py [--root OTHER_CHECKOUT]
+
+then compare the (kernel name, calls) columns of the two DIR/**/NAME_kernel_stats.csv: `python tools/truncate_launch_list.py --diff A B`."""
+import argparse
+import csv
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument('--diff', nargs=2, metavar='CSV')
+args = ap.parse_args()
+
+if args.diff:
+    def calls(path):
+        with open(path) as f:
+            return {row['Name']: int(row['Calls']) for row in csv.DictReader(f)}
+    a, b = calls(args.diff[0]), calls(args.diff[1])
+    differ = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+    print(f'{len(a)} kernels / {sum(a.values())} launches in {args.diff[0]}; {len(b)} / {sum(b.values())} in {args.diff[1]}; '
+          f'{len(differ)} kernels differ in name or count')
+    for k in differ:
+        print(f'  {a.get(k)} vs {b.get(k)}  {k}')
+    sys.exit(1 if differ else 0)
+
+ROOT = os.path.abspath(args.root)
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+import mmvid_amd  # noqa: E402
+from mmvid_amd.dalle_artv import DALLE  # noqa: E402
+from mmvid_amd.dalle_bert import BERT  # noqa: E402
+from mmvid_amd.vae import VQGanVAE1024  # noqa: E402
+
+assert os.path.abspath(mmvid_amd.__file__).startswith(ROOT), (mmvid_amd.__file__, ROOT)
+dev = torch.device('cuda', 0)
+
+
+def tiny_vae():
+    v = VQGanVAE1024(None, 64, ddconfig={'ch': 32}, n_embed=256)
+    v.image_size, v.num_tokens = 64, 256
+    return v
+
+
+kw = dict(dim=768, num_text_tokens=49408, text_seq_len=16, which_transformer='openai_clip_visual', num_targets=2, transformer_layers=2)
+torch.manual_seed(0)
+bert = BERT(vae=tiny_vae(), num_visuals=0, **kw).to(dev).eval()
+artv = DALLE(vae=tiny_vae(), cvae=None, num_visuals=1, **kw).to(dev).eval()
+text = torch.randint(1, 49408, (4, 16), device=dev)
+vis = torch.randint(0, 256, (4, 16), device=dev)
+mp = {'T1_n': 2, 'T2_n': 1, 'T3_n': 1, 'N1_n': 0.9, 'N2_n': 0.1, 'N3_n': 0.125, 'N4_n': 0.0625, 'T1_t': 2, 'T2_t': 1, 'T3_t': 1,
+      'N1_t': 0.5, 'N2_t': 0.2, 'N3_t': 0., 'N4_t': 0., 'T': 4, 'B': 2}
+for _ in range(2):
+    bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False)
+    bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False, guidance_scale=2.0, guidance_drop=('text', ))
+    artv.generate_images(text, visual=vis)  # batch 4: the captured five-launch step
+    artv.generate_images(text, visual=vis, filter_thres=0.999)  # a filter_thres that filters: the eager torch.topk path
+torch.cuda.synchronize()
+print('done')
