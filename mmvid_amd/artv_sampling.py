@@ -1,0 +1,150 @@
+"""The token loop of the ART-V sampler over the key/value cache (DALLE.generate_images, use_cache=True).
+
+One token = [head logits of the image block -> draw -> embedding row of the drawn token -> one decode step through the tower].  The
+position lives in the decode session (clip_tower.DecodeSession); the race variates come from torch's graph-safe device generator.
+`sample` picks launch_loop (separate launches, [draw -> advance] per token: captured once and replayed in production; eager for injected
+variates, a `filter_thres` that filters, `stable` and up to 4 tokens) or, at batch 1-2, token_launch_loop (the whole token is ONE
+persistent launch, with a restart point from which launch_loop finishes the call when the device was shared under it)."""
+import os
+
+import torch
+
+from . import _lib, ops
+
+
+def k_keep(filter_thres, total):
+    return max(int((1 - filter_thres) * total), 1)
+
+
+def keep_top(logits, k):
+    """dalle_artv.py:61-67: each row's k largest logits, -inf elsewhere (the logits themselves when k covers the row)."""
+    if k >= logits.shape[-1]:
+        return logits
+    val, ind = torch.topk(logits, k)
+    return torch.full_like(logits, float('-inf')).scatter_(1, ind, val)
+
+
+class TokenLoop:
+    """The buffers of one sampling call and the two halves of a token, draw(step) and advance()."""
+
+    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc):
+        B, dev = h.shape[0], h.device
+        c0, c1 = model._allowed_range(model.control_seq_len)
+        self.model, self.ln, self.first_pos, self.temperature, self.race, self.trunc = model, model.to_logits[0], first_pos, temperature, race, trunc
+        self.V, self.steps, self.k_keep = c1 - c0, model.target_seq_len, k_keep(filter_thres, model.total_tokens)
+        self.w_blk, self.b_blk = model._w16()[c0:c1], model.to_logits[1].bias.detach()[c0:c1].contiguous()
+        self.pos_rows, self.iemb = model._pos_rows().detach().contiguous(), model.image_emb.weight.detach()
+        self.sess = model.transformer.decode_session(cache, first_pos, graph=False)
+        self.out = torch.empty(B, self.steps, dtype=torch.long, device=dev)
+        self.hbuf, self.logits = h.clone(), torch.empty(B, self.V, device=dev)
+        self.tok, self.E = torch.empty(B, dtype=torch.long, device=dev), torch.empty(B, self.V, device=dev)
+        # production: the race variates of the whole loop in one draw (an exponential_ inside the captured step costs its launch and two
+        # generator-state fills per replay: 12 us per token); the draw of token n reads block n = position - first_pos.  Capped at 256 MB on top of
+        # the KV cache (batch 64 at 1,024 steps x 1,024 codes) and at the 1,024 rows the indexed draw kernel takes: larger calls draw per step
+        fits = race is None and self.steps * B * self.V <= (1 << 26) and B <= 1024
+        self.E_all = torch.empty(self.steps, B, self.V, device=dev).exponential_() if fits else None
+        self.hid = self.hbuf  # the hidden state the next draw reads: the prompt's last position, then the session's output buffer
+
+    def draw(self, step):
+        """The token of `step` into self.tok.  (`step` names the injected variates only: the pre-drawn ones are indexed by the position.)"""
+        src, ln, T = self.hid, self.ln, self.temperature
+        if self.model.stable:
+            self.hbuf.copy_(self.model.norm_by_max(src))
+            src = self.hbuf
+        ops.gemv_rows(src, self.w_blk, self.b_blk, ln=(ln.weight, ln.bias, ln.eps), round_in=True, out=self.logits)  # LN + head block
+        lg = keep_top(self.logits, self.k_keep)
+        if self.trunc is not None:
+            ops.logits_truncate(lg, self.trunc[0], self.trunc[1], logit_div=T, out=lg)
+        if self.E_all is not None:
+            ops.sample_race(lg, self.E_all, None, 0.0, logit_div=T, want_y=False, tok_out=self.tok, step_dev=self.sess.pos, step0=self.first_pos)
+            return
+        if self.race is not None:
+            self.E.copy_(self.race(f'tok{step}', tuple(self.E.shape)))
+        else:
+            self.E.exponential_()
+        ops.sample_race(lg, self.E, None, 0.0, logit_div=T, want_y=False, tok_out=self.tok)
+
+    def advance(self):
+        """The embedding row of the drawn token (the same launch files it in `out` at column pos - first_pos), then one position through the tower."""
+        ops.decode_embed(self.tok, self.iemb, self.pos_rows, self.sess.pos, self.sess.x, record=self.out, record_pos0=self.first_pos)
+        self.sess.advance()
+        self.hid = self.sess.y
+
+    def token(self, step=-1):
+        self.draw(step)
+        self.advance()
+
+    def decode_token(self):
+        """The argument block of the one-launch token (the tensors it points to stay alive in this object and in the model)."""
+        tk, ln = _lib.DecodeToken(), self.ln
+        tk.tok, tk.table, tk.table_rows, tk.pos_rows, tk.pos_off = self.tok.data_ptr(), self.iemb.data_ptr(), self.iemb.shape[0], self.pos_rows.data_ptr(), 0
+        tk.record, tk.record_ld, tk.record_pos0 = self.out.data_ptr(), self.out.stride(0), self.first_pos
+        tk.lnf_w, tk.lnf_b, tk.lnf_eps, tk.head_w, tk.head_b, tk.V = ln.weight.data_ptr(), ln.bias.data_ptr(), ln.eps, self.w_blk.data_ptr(), self.b_blk.data_ptr(), self.V
+        tk.E, tk.e_step_stride, tk.e_pos0, tk.temperature, tk.tok_offset, tk.logits_out = self.E_all.data_ptr(), self.E_all.stride(0), self.first_pos, self.temperature, 0, None
+        return tk
+
+    def finish(self):
+        self.out[:, self.steps - 1].copy_(self.tok)  # (the last token is never embedded, so no launch has filed it in `out`)
+        return [self.out[:, i:i + 1] for i in range(self.steps)]
+
+
+def launch_loop(loop, start=0, capture=False):
+    """Tokens start .. steps - 1 by separate launches: every token but the last is drawn and run through the tower, the last only drawn.
+    capture: two eager tokens have warmed every kernel; [draw -> advance] is then captured once and replayed."""
+    sess = loop.sess
+    for step in range(start, loop.steps - 1):
+        if sess.graph is not None:
+            sess.replay()
+            continue
+        loop.token(step)
+        if capture and step == 1:
+            sess.capture(loop.token)
+    loop.draw(loop.steps - 1)
+    toks = loop.finish()
+    sess.check()
+    return toks
+
+
+def token_launch_loop(loop):
+    """One persistent launch per token.  The first token is drawn from the prompt's hidden state the usual way; every launch then embeds
+    the token drawn last, files it in `out`, and draws the next one.  Restart point: the launch needs its 256 blocks resident together; if
+    the device is shared while it runs, a poll times out, the launch and all later ones on the session's workspace are void, and the
+    failure flag says so.  Every `_decode_check_every` tokens the flag is read (one sync per ~15 ms of work) and the token to embed next is
+    kept; after a failure the loop goes back to the last verified token and finishes with launch_loop (five launches per layer, eager)."""
+    sess, tok, steps, tk = loop.sess, loop.tok, loop.steps, loop.decode_token()
+    check_every, hook = loop.model._decode_check_every, loop.model._token_step_hook  # (hook, tests: called after every launch)
+    loop.draw(0)
+    direct = os.environ.get('MMVID_DECODE_TOKEN_GRAPH', '0') == '0'  # one kernel per token: launched directly (a one-node graph replay costs more)
+    good_step, good_tok = 0, tok.clone()
+    for step in range(1, steps):  # step = tokens launched so far
+        if sess.graph is not None:
+            sess.replay()
+        else:
+            sess.token_step(tk)
+            if step == 2 and not direct:
+                sess.capture(lambda: sess.token_step(tk))
+        if hook is not None:
+            hook(step, sess)
+        if step % check_every == 0 or step == steps - 1:
+            if sess.failed():
+                break
+            good_step = step
+            good_tok.copy_(tok)
+    else:
+        return loop.finish()
+    # a persistent launch failed somewhere after token `good_step` (which `tok` holds again): go on from there with the separate launches
+    tok.copy_(good_tok)
+    sess.fall_back(loop.first_pos + good_step)
+    loop.advance()
+    return launch_loop(loop, good_step + 1)
+
+
+def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None):
+    """h [B, dim]: the hidden state of the prompt's last position, `cache` filled below first_pos -> the sampled tokens, target_seq_len columns [B, 1]."""
+    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc)
+    capture = race is None and loop.k_keep >= loop.V and not model.stable and loop.steps > 4
+    # (the one-launch token has no truncation in it: a call with top_k / top_p takes the separate launches; MMVID_DECODE_TOKEN=0: all do)
+    if (capture and loop.sess.persistent and loop.E_all is not None and loop.V <= 2048 and trunc is None and
+            os.environ.get('MMVID_DECODE_TOKEN', '1') != '0'):
+        return token_launch_loop(loop)
+    return launch_loop(loop, 0, capture)

@@ -93,8 +93,8 @@ class DecodeSession:
         self.x = torch.zeros(B, tower.width, device=dev, dtype=torch.float32)
         self.y = torch.zeros_like(self.x)
         self.pos = torch.tensor([first_pos], dtype=torch.int32, device=dev)
-        self.host_pos = int(first_pos)  # host mirror of the device position (explicit: not derived from the number of step() calls)
-        self.graph, self.want_graph, self.calls = None, graph, 0
+        self.host_pos = int(first_pos)  # host mirror of the device position: advance(), token_step(), seek() and replay() move it, nothing else does
+        self.graph, self.graph_advance, self.want_graph, self.calls, self.fell_back = None, 0, graph, 0, 0
         self._slice_cfgs = {}
         # the whole step as one launch of 256 co-resident blocks (csrc/decode_persistent.hip) where the tower / batch / device allow it;
         # MMVID_DECODE_PERSISTENT=0 (or fused='launches') keeps the five-launches-per-layer form
@@ -125,6 +125,27 @@ class DecodeSession:
                   ops._p(self.cache), Lmax, ops._p(self.pos), 0, ops._p(self.scratch), ops._stream())
         self.pos.add_(1)
 
+    def advance(self):
+        """One position from self.x into self.y, in whatever form the session is in."""
+        self._enqueue()
+        self.host_pos += 1
+
+    def seek(self, pos):
+        """The next step runs at position `pos`: the device scalar and its host mirror together."""
+        self.pos.fill_(int(pos))
+        self.host_pos = int(pos)
+
+    def capture(self, fn):
+        """Record fn() -- launches that move this session through advance() / token_step(), and whatever else belongs to the caller's
+        step -- as this session's graph.  A capture enqueues nothing, so host_pos stays; replay() moves it by what fn advanced."""
+        at = self.host_pos
+        self.graph = ops.capture_graph(fn)
+        self.graph_advance, self.host_pos = self.host_pos - at, at
+
+    def replay(self):
+        self.graph.replay()
+        self.host_pos += self.graph_advance
+
     def token_step(self, tk):
         """The sampler's whole token in one launch (csrc/decode_persistent.hip: embedding of the token drawn last -> tower step -> head ->
         draw of the next token -> position + 1).  tk: a filled _lib.DecodeToken (the caller keeps its tensors alive).  Persistent sessions only."""
@@ -142,9 +163,8 @@ class DecodeSession:
         """Leave the persistent form for good: this session continues from position `pos` with the five-launch step (the key/value
         entries at and beyond `pos` are rewritten by the steps that follow)."""
         self.persistent, self.graph = False, None
-        self.fell_back = getattr(self, 'fell_back', 0) + 1
-        self.pos.fill_(int(pos))
-        self.host_pos = int(pos)
+        self.fell_back += 1
+        self.seek(pos)
 
     def check(self):
         """Raise if the persistent step failed and nobody recovered from it (`step(verify=True)` and the ART-V sampling loop do, by
@@ -162,23 +182,14 @@ class DecodeSession:
         self.x.copy_(x_new)
         self.calls += 1
         if self.want_graph and self.graph is None and self.calls == 2:
-            # second step: capture (the first one ran eagerly and warmed every kernel variant up)
-            g = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                with torch.cuda.graph(g, stream=side):
-                    self._enqueue()
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = g
+            self.capture(self.advance)  # second step: capture (the first one ran eagerly and warmed every kernel variant up)
         if self.graph is not None:
-            self.graph.replay()
+            self.replay()
         else:
-            self._enqueue()
+            self.advance()
         if verify and self.persistent and self.failed():
-            self.fall_back(self.host_pos)
-            self._enqueue()
-        self.host_pos += 1
+            self.fall_back(self.host_pos - 1)
+            self.advance()
         return self.y
 
 

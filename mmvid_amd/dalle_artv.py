@@ -9,13 +9,12 @@ materialised: each of the three position segments runs `to_logits` against ITS b
 MFMA GEMM + the fused cross-entropy kernels), which is the same loss with ~14x fewer head FLOPs and no [B, L, 51584]
 tensors.  Sampling keeps a per-layer key/value cache (the reference recomputes the whole prefix per token) and draws
 tokens with the device sampler of csrc/sample.hip."""
-import os
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib, ops, sampling
+from . import artv_sampling, ops, sampling
+from .artv_sampling import k_keep, keep_top
 from .clip_tower import OpenAICLIPTransformer
 from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
 from .frontend import Frontend, face_choices
@@ -31,10 +30,7 @@ def is_empty(t):
 
 def top_k(logits, thres=0.5):
     """dalle_artv.py:61-67: keep the k = max(int((1 - thres) * n), 1) largest logits of each row, -inf elsewhere."""
-    k = max(int((1 - thres) * logits.shape[-1]), 1)
-    kept = torch.full_like(logits, float('-inf'))
-    val, ind = torch.topk(logits, k)
-    return kept.scatter_(1, ind, val)
+    return keep_top(logits, k_keep(thres, logits.shape[-1]))
 
 
 class DALLE(nn.Module):
@@ -87,6 +83,8 @@ class DALLE(nn.Module):
         self.eraser = dict(p=1.0, scale=(0.4, 0.8), ratio=(0.5, 2.0))  # RandomErasing(value=-1), dalle_artv.py:229-232
         self.frontend = Frontend(seed=kwargs.get('frontend_seed'))
         self._w16_cache = None
+        # (artv_sampling.token_launch_loop: reads the failure flag every so many tokens; tests: hook(tokens launched so far, session) after every launch)
+        self._decode_check_every, self._token_step_hook = 64, None
         seg = [0] * (text_seq_len + 1) + [1] * self.visual_seq_len + [2] * self.target_seq_len
         self.register_buffer('_seg', torch.tensor(seg, dtype=torch.int32), persistent=False)
 
@@ -289,166 +287,17 @@ class DALLE(nn.Module):
         total_tokens classes keeps k = int((1 - thres) * total_tokens) of them; the classes outside the block sit at -max,
         so the filter only ever removes block classes when k is smaller than the block."""
         B, n = block_logits.shape
-        k_keep = max(int((1 - filter_thres) * self.total_tokens), 1)
-        if k_keep < n:
-            kept = torch.full_like(block_logits, float('-inf'))
-            val, ind = torch.topk(block_logits, k_keep)
-            block_logits = kept.scatter_(1, ind, val)
-        block_logits = block_logits.contiguous()
+        block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens)).contiguous()
         if trunc is not None:  # top-k / nucleus of what filter_thres left (ops.logits_truncate)
             block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logit_div=temperature)
         E = race(name, (B, n)) if race is not None else ops.exponential_like((B, n), block_logits.device)
         tok, _ = ops.sample_race(block_logits, E, None, 0.0, logit_div=temperature, want_y=False)
         return tok.view(B, 1)
 
-    def _sample_cached(self, h, cache, first_pos, filter_thres, temperature, race, trunc=None):
-        """The sampling loop over the key/value cache.  One token = [head logits of the image block -> draw -> embedding
-        row of the drawn token -> one decode step through the tower]; that chain is captured once (hipGraph) and replayed
-        per token: the position lives in a device scalar the step advances, the race variates come from torch's
-        graph-safe device generator.  Injected variates (`race`, tests) or a `filter_thres` that actually filters run the same
-        kernels eagerly.  `trunc` = (top_k, top_p) adds ONE launch between the head and the draw (ops.logits_truncate, in place on
-        the logits the draw reads); it is captured with the rest and does not bear on `use_graph`."""
-        B, dev = h.shape[0], h.device
-        c0, c1 = self._allowed_range(self.control_seq_len)
-        V = c1 - c0
-        lin, ln = self.to_logits[1], self.to_logits[0]
-        w_blk, b_blk = self._w16()[c0:c1], lin.bias.detach()[c0:c1].contiguous()
-        pos_rows = self._pos_rows().detach().contiguous()
-        iemb = self.image_emb.weight.detach()
-        sess = self.transformer.decode_session(cache, first_pos, graph=False)
-        k_keep = max(int((1 - filter_thres) * self.total_tokens), 1)
-        steps = self.target_seq_len
-        out = torch.empty(B, steps, dtype=torch.long, device=dev)
-        hbuf, logits = h.clone(), torch.empty(B, V, device=dev)
-        tok, E = torch.empty(B, dtype=torch.long, device=dev), torch.empty(B, V, device=dev)
-        # production: the race variates of the whole loop in one draw (an exponential_ inside the captured step costs its launch and two
-        # generator-state fills per replay: 12 us per token); the draw of token n reads block n = position - first_pos.  Capped at
-        # 256 MB on top of the KV cache (batch 64 at 1,024 steps x 1,024 codes) and at the 1,024 rows the indexed draw kernel takes: larger
-        # calls draw per step (the `E.exponential_()` path below)
-        E_all = torch.empty(steps, B, V, device=dev).exponential_() if (race is None and steps * B * V <= (1 << 26) and B <= 1024) else None
-
-        hid = [hbuf]  # the hidden state the next draw reads: the prompt's last position, then the session's output buffer
-
-        def draw(step):
-            src = hid[0]
-            if self.stable:
-                hbuf.copy_(self.norm_by_max(src))
-                src = hbuf
-            ops.gemv_rows(src, w_blk, b_blk, ln=(ln.weight, ln.bias, ln.eps), round_in=True, out=logits)  # LN + head block
-            lg = logits
-            if k_keep < V:
-                val, ind = torch.topk(lg, k_keep)
-                lg = torch.full_like(lg, float('-inf')).scatter_(1, ind, val)
-            if trunc is not None:
-                ops.logits_truncate(lg, trunc[0], trunc[1], logit_div=temperature, out=lg)
-            if E_all is not None:
-                ops.sample_race(lg, E_all, None, 0.0, logit_div=temperature, want_y=False, tok_out=tok, step_dev=sess.pos, step0=first_pos)
-                return
-            if race is not None:
-                E.copy_(race(f'tok{step}', (B, V)))
-            else:
-                E.exponential_()
-            ops.sample_race(lg, E, None, 0.0, logit_div=temperature, want_y=False, tok_out=tok)
-
-        def advance():
-            # the embedding row of the drawn token (which the same launch files in `out` at column pos - first_pos), then one position
-            # through the tower; advances sess.pos
-            ops.decode_embed(tok, iemb, pos_rows, sess.pos, sess.x, record=out, record_pos0=first_pos)
-            sess._enqueue()
-            sess.host_pos += 1  # (the host mirror of the device position: DecodeSession keeps it for step() / token_step() itself)
-            hid[0] = sess.y
-
-        graph = None
-        use_graph = race is None and k_keep >= V and not self.stable and steps > 4
-        # batch 1-2 in production: the whole token (embedding -> tower -> head -> draw) is ONE persistent launch (MMVID_DECODE_TOKEN=0: the
-        # launches below).  The first token is drawn from the prompt's hidden state the usual way; every launch then embeds the token drawn
-        # last, files it in `out`, and draws the next one.
-        # (that launch has no truncation in it: a call with top_k / top_p takes the launches below)
-        if (use_graph and sess.persistent and E_all is not None and V <= 2048 and trunc is None and
-                os.environ.get('MMVID_DECODE_TOKEN', '1') != '0'):
-            tk = _lib.DecodeToken()
-            tk.tok, tk.table, tk.table_rows, tk.pos_rows, tk.pos_off = tok.data_ptr(), iemb.data_ptr(), iemb.shape[0], pos_rows.data_ptr(), 0
-            tk.record, tk.record_ld, tk.record_pos0 = out.data_ptr(), out.stride(0), first_pos
-            lnw, lnb = ln.weight.detach(), ln.bias.detach()
-            tk.lnf_w, tk.lnf_b, tk.lnf_eps, tk.head_w, tk.head_b, tk.V = lnw.data_ptr(), lnb.data_ptr(), ln.eps, w_blk.data_ptr(), b_blk.data_ptr(), V
-            tk.E, tk.e_step_stride, tk.e_pos0, tk.temperature, tk.tok_offset, tk.logits_out = E_all.data_ptr(), B * V, first_pos, temperature, 0, None
-            draw(0)
-            direct = os.environ.get('MMVID_DECODE_TOKEN_GRAPH', '0') == '0'  # one kernel per token: launched directly (a one-node graph replay costs more)
-            # Restart point.  The launch needs its 256 blocks resident together; if the device is shared while it runs, a poll times
-            # out, the launch and all later ones on the session's workspace are void, and the failure flag says so.  Every CHECK tokens
-            # the flag is read (one sync per ~15 ms of work) and the token to embed next is kept; after a failure the loop goes back to
-            # the last verified token and finishes with the launches below (five per layer), which need no co-residency.
-            CHECK = getattr(self, '_decode_check_every', 64)
-            hook = getattr(self, '_token_step_hook', None)  # tests: called as hook(tokens launched so far, session) after every launch
-            good_step, good_tok = 0, tok.clone()
-            step = 0
-            while step < steps - 1:
-                if graph is not None:
-                    graph.replay()
-                    sess.host_pos += 1
-                else:
-                    sess.token_step(tk)
-                    if step == 1 and not direct:
-                        graph = torch.cuda.CUDAGraph()
-                        side = torch.cuda.Stream()
-                        side.wait_stream(torch.cuda.current_stream())
-                        with torch.cuda.stream(side):
-                            with torch.cuda.graph(graph, stream=side):
-                                sess.token_step(tk)
-                        sess.host_pos -= 1  # (the capture enqueued nothing)
-                        torch.cuda.current_stream().wait_stream(side)
-                step += 1
-                if hook is not None:
-                    hook(step, sess)
-                if step % CHECK == 0 or step == steps - 1:
-                    if sess.failed():
-                        break
-                    good_step = step
-                    good_tok.copy_(tok)
-            else:
-                out[:, steps - 1].copy_(tok)
-                return [out[:, i:i + 1] for i in range(steps)]
-            # a persistent launch failed somewhere after token `good_step`: go on from there with the separate launches
-            tok.copy_(good_tok)
-            sess.fall_back(first_pos + good_step)
-            graph = None
-            for step in range(good_step, steps - 1):
-                if step > good_step:
-                    draw(step)
-                advance()
-            draw(steps - 1)
-            out[:, steps - 1].copy_(tok)
-            return [out[:, i:i + 1] for i in range(steps)]
-        for step in range(steps - 1):  # every token but the last: draw it, then run it through the tower
-            if graph is not None:
-                graph.replay()
-                sess.host_pos += 1
-                continue
-            draw(step)
-            advance()
-            if use_graph and step == 1:
-                # two eager steps have warmed every kernel; capture [draw -> advance] once and replay it
-                graph = torch.cuda.CUDAGraph()
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    with torch.cuda.graph(graph, stream=side):
-                        draw(-1)
-                        advance()
-                sess.host_pos -= 1  # (the capture enqueued nothing)
-                torch.cuda.current_stream().wait_stream(side)
-        draw(steps - 1)
-        out[:, steps - 1].copy_(tok)
-        sess.check()
-        return [out[:, i:i + 1] for i in range(steps)]
-
     def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None):
         """The probability vector `_draw` samples from (tests compare it with the reference's full-width expression)."""
         trunc = self._truncation(top_k, top_p, block_logits.shape[1])
-        k_keep = max(int((1 - filter_thres) * self.total_tokens), 1)
-        if k_keep < block_logits.shape[1]:
-            val, ind = torch.topk(block_logits, k_keep)
-            block_logits = torch.full_like(block_logits, float('-inf')).scatter_(1, ind, val)
+        block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens))
         if trunc is not None:
             block_logits = ops.logits_truncate(block_logits.contiguous(), trunc[0], trunc[1], logit_div=temperature)
         return F.softmax(block_logits / temperature, dim=-1)
@@ -478,7 +327,7 @@ class DALLE(nn.Module):
             cache = self.transformer.new_kv_cache(B, self.total_seq_len, text.device)
             prompt = torch.cat(self._prompt_ids(text, vis_tok), 1)  # <bos> text visual: positions 0 .. cl
             h = self.transformer.prefill(self._embed_rows(prompt, 0), cache)[:, -1, :].contiguous()
-            toks = self._sample_cached(h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc)
+            toks = artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc)
         else:
             image = torch.empty(B, 0, dtype=torch.long, device=text.device)
             for step in range(self.target_seq_len):

@@ -23,6 +23,17 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def capture_graph(fn):
+    """fn() recorded as a hipGraph on a side stream (nothing runs; whatever fn launches must have run eagerly before, so that every
+    kernel variant is loaded) -> the torch.cuda.CUDAGraph to replay on the current stream."""
+    g, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side), torch.cuda.graph(g, stream=side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    return g
+
+
 _DET_WS = {}  # (operator, device, bytes) -> uint8 workspace of a deterministic form, cached per shape
 
 

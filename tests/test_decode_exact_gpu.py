@@ -98,8 +98,7 @@ def _launch_positions(rig, ns, what):
     for n in ns:
         pos = n - 1
         rig.prepare(pos)
-        sess.pos.fill_(pos)
-        sess.host_pos = pos
+        sess.seek(pos)
         rig.check(sess, pos, f'{what} n={n}')
 
 

@@ -121,8 +121,8 @@ def test_gemv_rows_mfma_form_vs_torch():
 
 
 def test_artv_sampler_recovers_from_a_failed_persistent_launch(golden):
-    """ADVICE r5: the recovery branch of the one-launch sampler (dalle_artv.py::_sample_cached) -- restore the last verified token,
-    sess.fall_back(first_pos + good_step), finish with draw() / advance().  The failure flag (workspace word 1) is raised from a hook
+    """ADVICE r5: the recovery branch of the one-launch sampler (artv_sampling.py::token_launch_loop) -- restore the last verified token,
+    sess.fall_back(first_pos + good_step), finish with launch_loop().  The failure flag (workspace word 1) is raised from a hook
     after 13 of 31 launches with the flag read every 8 tokens: tokens 0..7 stand, 8..31 are redone with the launch-per-layer step.
     Same seed, same variates: the tokens must equal a run that never used the one-launch step (MMVID_DECODE_TOKEN=0)."""
     import os
@@ -161,8 +161,44 @@ def test_artv_sampler_recovers_from_a_failed_persistent_launch(golden):
     assert torch.equal(a_img, b_img), 'recovered run differs from the launch-per-layer run on the same variates'
 
 
+def test_artv_sampler_keeps_the_session_position_on_every_path(monkeypatch):
+    """The host mirror of the decode session's position (DecodeSession.host_pos) against the device scalar after a whole sampling call
+    on each path of artv_sampling.py: one launch per token (batch 2), the captured launches on a persistent session (batch 2,
+    MMVID_DECODE_TOKEN=0), the captured five-launch step (batch 4) and the eager loop (batch 4, injected variates).  32 tokens = 31
+    steps through the tower from position 33; the captured paths replay at least 28 of them, the other two none."""
+    from mmvid_amd.dalle_artv import DALLE
+    from test_host_logic import tiny_vae
+    torch.manual_seed(71)
+    m = DALLE(dim=768, vae=tiny_vae(), cvae=None, num_text_tokens=49408, text_seq_len=16, which_transformer='openai_clip_visual',
+              num_visuals=1, num_targets=2, transformer_layers=2).to(DEV).eval()
+    gen = torch.Generator().manual_seed(72)
+    text, vis = torch.randint(1, 49408, (4, 16), generator=gen).to(DEV), torch.randint(0, 256, (4, 16), generator=gen).to(DEV)
+    steps, first_pos = m.target_seq_len, m.control_seq_len + 1
+    assert steps == 32
+    made, replays = [], []
+    inner = m.transformer.decode_session
+    monkeypatch.setattr(m.transformer, 'decode_session', lambda *a, **k: (made.append(inner(*a, **k)), made[-1])[1])
+    replay = torch.cuda.CUDAGraph.replay
+    monkeypatch.setattr(torch.cuda.CUDAGraph, 'replay', lambda self: (replays.append(1), replay(self))[1])
+    cases = [('one launch per token', 2, None, {}, False), ('captured launches, persistent session', 2, '0', {}, True),
+             ('captured five-launch step', 4, None, {}, True),
+             ('eager, injected variates', 4, None, dict(_race=lambda name, shape: torch.ones(shape, device=DEV)), False)]
+    for what, B, token_env, kw, captured in cases:
+        del made[:], replays[:]
+        if token_env is not None:
+            monkeypatch.setenv('MMVID_DECODE_TOKEN', token_env)
+        m.generate_images(text[:B], visual=vis[:B], **kw)
+        monkeypatch.delenv('MMVID_DECODE_TOKEN', raising=False)
+        assert len(made) == 1, what
+        sess = made[0]
+        print(f'{what}: host_pos {sess.host_pos}, device {int(sess.pos)}, {len(replays)} replays, persistent {sess.persistent}, fell back {sess.fell_back}')
+        assert sess.host_pos == int(sess.pos) == first_pos + steps - 1, what
+        assert len(replays) >= steps - 4 if captured else not replays, what
+
+
 @pytest.mark.parametrize('N,H', [(3, 6), (1, 128), (2, 2)])
 def test_conv_in_kernel_vs_torch(N, H):
+
     """csrc/conv.hip::conv_in_kernel (the full-size encoder's first layer: 3(8) -> 128 channels on 128-pixel-wide frames; two image rows per
     block, weights in registers, stores straight from the accumulators): bf16 and fp32 outputs and the bf16-pair operator against an
     fp64 convolution of the same rounded operands; the GroupNorm partial sums (one block per image row) against sums of what it stored."""

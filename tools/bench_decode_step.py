@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a cached ART-V decode step spends its time: each launch kind of the fused step alone (HIP events, 50 reps), the
-whole 12-layer step eagerly and as a graph replay, and the complete per-token chain of DALLE._sample_cached."""
+whole 12-layer step eagerly and as a graph replay, and the complete per-token chain of the sampler (mmvid_amd/artv_sampling.py)."""
 import ctypes
 import os
 import sys
@@ -49,22 +49,16 @@ for first in (129, 1100):
         sess.x.normal_()
 
         def step():
-            sess.pos.fill_(first)
-            sess._enqueue()
+            sess.seek(first)
+            sess.advance()
 
         t = timeit(step, 20)
         print(f'tower decode step at position {first}, fused={fused}: {t:.1f} us eager')
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                sess._enqueue()
-        torch.cuda.current_stream().wait_stream(s)
+        sess.capture(sess.advance)
 
         def rep():
-            sess.pos.fill_(first)
-            g.replay()
+            sess.seek(first)
+            sess.replay()
 
         print(f'   as a graph replay: {timeit(rep, 20):.1f} us')
 text = torch.randint(1, 49408, (B, 64), device=dev)
@@ -87,11 +81,5 @@ def chain():
 
 
 print('60 dependent trivial kernels, eager: %.1f us' % timeit(chain, 20))
-g = torch.cuda.CUDAGraph()
-s = torch.cuda.Stream()
-s.wait_stream(torch.cuda.current_stream())
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        chain()
-torch.cuda.current_stream().wait_stream(s)
+g = ops.capture_graph(chain)
 print('60 dependent trivial kernels, graph replay: %.1f us  (= the floor of a 60-launch decode step on this box)' % timeit(g.replay, 20))

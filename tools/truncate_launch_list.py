@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""The calls of both samplers WITHOUT the truncation keywords, on the tiny models of the tests, for a kernel-trace run: the kernel list of
-this tree must be the parent commit's (no launch added, none changed).
+"""The calls of both samplers on the tiny models of the tests, for a kernel-trace run: the kernel list of this tree must be the parent
+commit's (no launch added, none changed).  BERT and ART-V without the truncation keywords, and ART-V on every path of its token loop
+(mmvid_amd/artv_sampling.py): batch 4 captured, batch 4 with a `filter_thres` that filters (eager), batch 4 with top_k = 8 (captured with
+the truncation launch) and batch 2 (one launch per token).  Every ART-V call runs under a fixed seed and prints a digest of the token
+tensor it sampled: the two trees' outputs must be equal line for line.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python tools/truncate_launch_list.py [--root OTHER_CHECKOUT]
 
 then compare the (kernel name, calls) columns of the two DIR/**/NAME_kernel_stats.csv: `python tools/truncate_launch_list.py --diff A B`."""
 import argparse
 import csv
+import hashlib
 import os
 import sys
 
@@ -54,10 +58,24 @@ text = torch.randint(1, 49408, (4, 16), device=dev)
 vis = torch.randint(0, 256, (4, 16), device=dev)
 mp = {'T1_n': 2, 'T2_n': 1, 'T3_n': 1, 'N1_n': 0.9, 'N2_n': 0.1, 'N3_n': 0.125, 'N4_n': 0.0625, 'T1_t': 2, 'T2_t': 1, 'T3_t': 1,
       'N1_t': 0.5, 'N2_t': 0.2, 'N3_t': 0., 'N4_t': 0., 'T': 4, 'B': 2}
+decode = artv.vae.decode
+artv.vae.decode = lambda seq: (sampled.append(seq.clone()), decode(seq))[1]
+sampled = []
+
+
+def artv_call(what, B, **kw):
+    torch.manual_seed(7)
+    artv.generate_images(text[:B], visual=vis[:B], **kw)
+    tokens = sampled.pop().cpu()
+    print(f'artv {what}: tokens {tuple(tokens.shape)} sha256 {hashlib.sha256(tokens.numpy().tobytes()).hexdigest()[:16]}')
+
+
 for _ in range(2):
     bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False)
     bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False, guidance_scale=2.0, guidance_drop=('text', ))
-    artv.generate_images(text, visual=vis)  # batch 4: the captured five-launch step
-    artv.generate_images(text, visual=vis, filter_thres=0.999)  # a filter_thres that filters: the eager torch.topk path
+    artv_call('batch 4', 4)  # the captured five-launch step
+    artv_call('batch 4, filter_thres 0.999', 4, filter_thres=0.999)  # a filter_thres that filters: the eager torch.topk path
+    artv_call('batch 4, top_k 8', 4, top_k=8)  # [head -> truncate -> draw -> embed -> tower] captured
+    artv_call('batch 2', 2)  # one persistent launch per token
 torch.cuda.synchronize()
 print('done')
