@@ -419,6 +419,12 @@ int mmvid_decode_embed(const int64_t* tok, const float* table, int64_t table_row
 int mmvid_decode_embed_record(const int64_t* tok, const float* table, int64_t table_rows, const float* pos_rows,
                               const int32_t* pos_dev, int pos_off, int B, int E, float* x, int64_t* record, int64_t record_ld,
                               int record_pos0, void* stream);
+/* ... for `groups` copies of the batch (the guided ART-V sampler, dalle_artv.py:274-281 with two prompts: the drawn token enters the tower
+ * on the conditional and on the unconditional row): x [groups * B][E], x[g * B + b] = table[tok[b]] + pos_rows[*pos_dev + pos_off] for every
+ * g < groups; record [B][record_ld] as above, written once per b.  groups == 1 writes the bytes of mmvid_decode_embed_record; groups >= 1. */
+int mmvid_decode_embed_record_groups(const int64_t* tok, const float* table, int64_t table_rows, const float* pos_rows,
+                                     const int32_t* pos_dev, int pos_off, int B, int groups, int E, float* x, int64_t* record,
+                                     int64_t record_ld, int record_pos0, void* stream);
 /* building blocks: append K|V rows of qkv [B*L, ldq] at positions pos..pos+L-1, and one-query attention over the
  * cached positions 0..pos (head_dim 64, Lmax <= 4096).  kv_store writes those rows of the cache only; attention_decode reads the Q
  * part of its qkv rows and the cache rows 0..pos only (rows beyond pos need not be finite). */
@@ -486,6 +492,13 @@ int mmvid_sample_race_at(const float* logits, int64_t ld, const float* E, const 
 int mmvid_sample_race_guided(const float* logits_c, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
                              const float* E, const float* noise_u, float temperature, float logit_div, int64_t R, int V,
                              int64_t tok_offset, int64_t* tok, float* y, void* stream);
+/* The ART-V token draw under guidance (dalle_artv.py:274-281 on two logit rows): the token-only, block-per-row form of
+ * mmvid_sample_race_at on the guided value of mmvid_sample_race_guided (same ld, scale_dev [R / rows_per_scale], R % rows_per_scale == 0),
+ * divided by logit_div.  E is block (*step_dev - step0) of [draws][R][V] (e_step_stride = R * V), or the [R][V] block itself when
+ * step_dev == NULL.  The token is that of mmvid_sample_race_guided without noise, bit for bit.  R <= 1024, ld >= V >= 1.  No atomics. */
+int mmvid_sample_race_guided_at(const float* logits_c, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
+                                const float* E, const int32_t* step_dev, int step0, int64_t e_step_stride, float logit_div, int64_t R,
+                                int V, int64_t tok_offset, int64_t* tok, void* stream);
 /* Top-k and nucleus (top-p) truncation of the logits both samplers draw from (dalle_bert.py:527-534: BERT draws from the full softmax;
  * dalle_artv.py:61-67,274-276: ART-V's top_k filter), on the device.  Per row r: g_c = logits[r][c], or with logits_u != NULL the
  * guided value of mmvid_sample_race_guided (same ld, scale_dev [R / rows_per_scale], R % rows_per_scale == 0).  The classes are

@@ -187,6 +187,8 @@ SIGNATURES = {
     'mmvid_sample_race_guided': [P, P, I64, P, I64, P, P, F, F, I64, I, I64, P, P, P],
     'mmvid_cond_drop': [P, P, I, I, I, P, U64, F, F, P, I64, P, P, P, P],
     'mmvid_logits_truncate': [P, P, I64, P, I64, F, I, F, I64, I, P, I64, P, P],
+    'mmvid_sample_race_guided_at': [P, P, I64, P, I64, P, P, I, I64, F, I64, I, I64, P, P],
+    'mmvid_decode_embed_record_groups': [P, P, I64, P, P, I, I, I, I, P, P, I64, I, P],
 }
 OTHER = {'mmvid_last_error': ([], c_char_p), 'mmvid_abi_version': ([], I), 'mmvid_device_count': ([], I),
          'mmvid_warp_params_bytes': ([], I), 'mmvid_gemm_dw_multi_fill': ([I, P, I], ctypes.c_double),

@@ -4,7 +4,13 @@ One token = [head logits of the image block -> draw -> embedding row of the draw
 position lives in the decode session (clip_tower.DecodeSession); the race variates come from torch's graph-safe device generator.
 `sample` picks launch_loop (separate launches, [draw -> advance] per token: captured once and replayed in production; eager for injected
 variates, a `filter_thres` that filters, `stable` and up to 4 tokens) or, at batch 1-2, token_launch_loop (the whole token is ONE
-persistent launch, with a restart point from which launch_loop finishes the call when the device was shared under it)."""
+persistent launch, with a restart point from which launch_loop finishes the call when the device was shared under it).
+
+Classifier-free guidance (`guide`: one fp32 scale per video, on the device): the cache, the session and the head rows hold 2B sequences,
+rows 0..B-1 under the conditional prompt and rows B..2B-1 under the unconditional one.  One head launch gives both logit blocks, the
+draw races lc + w * (lc - lu) (mmvid_sample_race_guided_at, or the guided truncation followed by the plain draw), and the embedding
+launch writes the drawn token's row for both halves: the launches of a guided token are the unguided token's, and launch_loop
+captures them the same way.  A guided call never takes token_launch_loop."""
 import os
 
 import torch
@@ -27,46 +33,78 @@ def keep_top(logits, k):
 class TokenLoop:
     """The buffers of one sampling call and the two halves of a token, draw(step) and advance()."""
 
-    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc):
-        B, dev = h.shape[0], h.device
+    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide=None, trace=None):
+        rows, dev = h.shape[0], h.device  # the tower's rows: B, or 2B under guidance (h = [conditional; unconditional])
+        B = rows // 2 if guide is not None else rows
         c0, c1 = model._allowed_range(model.control_seq_len)
         self.model, self.ln, self.first_pos, self.temperature, self.race, self.trunc = model, model.to_logits[0], first_pos, temperature, race, trunc
+        self.guide, self.trace = guide, trace
         self.V, self.steps, self.k_keep = c1 - c0, model.target_seq_len, k_keep(filter_thres, model.total_tokens)
         self.w_blk, self.b_blk = model._w16()[c0:c1], model.to_logits[1].bias.detach()[c0:c1].contiguous()
         self.pos_rows, self.iemb = model._pos_rows().detach().contiguous(), model.image_emb.weight.detach()
         self.sess = model.transformer.decode_session(cache, first_pos, graph=False)
         self.out = torch.empty(B, self.steps, dtype=torch.long, device=dev)
-        self.hbuf, self.logits = h.clone(), torch.empty(B, self.V, device=dev)
+        self.hbuf, self.logits = h.clone(), torch.empty(rows, self.V, device=dev)
+        self.lc, self.lu = self.logits[:B], self.logits[B:]  # (guided: the two branches, one row stride)
+        self.lt = torch.empty(B, self.V, device=dev) if guide is not None and trunc is not None else None  # the guided, truncated value
         self.tok, self.E = torch.empty(B, dtype=torch.long, device=dev), torch.empty(B, self.V, device=dev)
         # production: the race variates of the whole loop in one draw (an exponential_ inside the captured step costs its launch and two
         # generator-state fills per replay: 12 us per token); the draw of token n reads block n = position - first_pos.  Capped at 256 MB on top of
         # the KV cache (batch 64 at 1,024 steps x 1,024 codes) and at the 1,024 rows the indexed draw kernel takes: larger calls draw per step
-        fits = race is None and self.steps * B * self.V <= (1 << 26) and B <= 1024
+        fits = race is None and trace is None and self.steps * B * self.V <= (1 << 26) and B <= 1024
         self.E_all = torch.empty(self.steps, B, self.V, device=dev).exponential_() if fits else None
         self.hid = self.hbuf  # the hidden state the next draw reads: the prompt's last position, then the session's output buffer
 
     def draw(self, step):
         """The token of `step` into self.tok.  (`step` names the injected variates only: the pre-drawn ones are indexed by the position.)"""
         src, ln, T = self.hid, self.ln, self.temperature
+        rec = None
+        if self.trace is not None:
+            rec = {}
+            self.trace.append(rec)
         if self.model.stable:
             self.hbuf.copy_(self.model.norm_by_max(src))
             src = self.hbuf
         ops.gemv_rows(src, self.w_blk, self.b_blk, ln=(ln.weight, ln.bias, ln.eps), round_in=True, out=self.logits)  # LN + head block
-        lg = keep_top(self.logits, self.k_keep)
-        if self.trunc is not None:
-            ops.logits_truncate(lg, self.trunc[0], self.trunc[1], logit_div=T, out=lg)
+        if rec is not None:
+            rec['logits'] = self.logits.clone()
+        lg = None  # what the plain draw reads; None: the guided draw reads both branches
+        if self.guide is None:
+            lg = keep_top(self.logits, self.k_keep)
+            if self.trunc is not None:
+                lg = ops.logits_truncate(lg, self.trunc[0], self.trunc[1], logit_div=T, out=lg, want_kept=rec is not None)
+        elif self.trunc is not None:  # the nucleus is the guided distribution's; what it leaves goes through the plain draw
+            lg = ops.logits_truncate(self.lc, self.trunc[0], self.trunc[1], logits_u=self.lu, scale=self.guide, rows_per_scale=1, logit_div=T,
+                                     out=self.lt, want_kept=rec is not None)
+        if rec is not None and self.trunc is not None:
+            lg, rec['kept'] = lg
+            rec['logits_t'] = lg.clone()
         if self.E_all is not None:
-            ops.sample_race(lg, self.E_all, None, 0.0, logit_div=T, want_y=False, tok_out=self.tok, step_dev=self.sess.pos, step0=self.first_pos)
-            return
-        if self.race is not None:
-            self.E.copy_(self.race(f'tok{step}', tuple(self.E.shape)))
+            E, at = self.E_all, dict(step_dev=self.sess.pos, step0=self.first_pos)
         else:
-            self.E.exponential_()
-        ops.sample_race(lg, self.E, None, 0.0, logit_div=T, want_y=False, tok_out=self.tok)
+            E, at = self.E, {}
+            if self.race is not None:
+                E.copy_(self.race(f'tok{step}', tuple(E.shape)))
+            else:
+                E.exponential_()
+        if lg is None:
+            ops.sample_race_guided_at(self.lc, self.lu, self.guide, 1, E, logit_div=T, tok_out=self.tok, **at)
+        else:
+            ops.sample_race(lg, E, None, 0.0, logit_div=T, want_y=False, tok_out=self.tok, **at)
+        if rec is not None:
+            rec['E'], rec['tok'] = E.clone(), self.tok.clone()
+            if self.guide is not None:
+                rec['scale'] = self.guide.clone()
 
     def advance(self):
-        """The embedding row of the drawn token (the same launch files it in `out` at column pos - first_pos), then one position through the tower."""
-        ops.decode_embed(self.tok, self.iemb, self.pos_rows, self.sess.pos, self.sess.x, record=self.out, record_pos0=self.first_pos)
+        """The embedding row of the drawn token (the same launch files it in `out` at column pos - first_pos), then one position through the
+        tower.  Guided: the row goes to both halves of the session's input."""
+        if self.guide is not None:
+            ops.decode_embed_groups(self.tok, self.iemb, self.pos_rows, self.sess.pos, self.sess.x, 2, record=self.out, record_pos0=self.first_pos)
+        else:
+            ops.decode_embed(self.tok, self.iemb, self.pos_rows, self.sess.pos, self.sess.x, record=self.out, record_pos0=self.first_pos)
+        if self.trace is not None:
+            self.trace[-1]['x_in'] = self.sess.x.clone()
         self.sess.advance()
         self.hid = self.sess.y
 
@@ -139,12 +177,15 @@ def token_launch_loop(loop):
     return launch_loop(loop, good_step + 1)
 
 
-def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None):
-    """h [B, dim]: the hidden state of the prompt's last position, `cache` filled below first_pos -> the sampled tokens, target_seq_len columns [B, 1]."""
-    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc)
-    capture = race is None and loop.k_keep >= loop.V and not model.stable and loop.steps > 4
-    # (the one-launch token has no truncation in it: a call with top_k / top_p takes the separate launches; MMVID_DECODE_TOKEN=0: all do)
-    if (capture and loop.sess.persistent and loop.E_all is not None and loop.V <= 2048 and trunc is None and
+def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None, guide=None, trace=None):
+    """h [B, dim]: the hidden state of the prompt's last position, `cache` filled below first_pos -> the sampled tokens, target_seq_len columns [B, 1].
+    guide (fp32 [B] on the device): h and the cache hold 2B sequences, conditional then unconditional.  trace (a list): one dict of clones
+    per token (logits, E, tok, x_in for every token but the last; scale when guided; logits_t and kept when truncated), eager loop."""
+    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide, trace)
+    capture = race is None and trace is None and loop.k_keep >= loop.V and not model.stable and loop.steps > 4
+    # (the one-launch token has no truncation and no second branch in it: a call with top_k / top_p or guidance takes the separate
+    # launches; MMVID_DECODE_TOKEN=0: all do)
+    if (capture and loop.sess.persistent and loop.E_all is not None and loop.V <= 2048 and trunc is None and guide is None and
             os.environ.get('MMVID_DECODE_TOKEN', '1') != '0'):
         return token_launch_loop(loop)
     return launch_loop(loop, 0, capture)

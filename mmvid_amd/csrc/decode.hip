@@ -808,6 +808,24 @@ __global__ __launch_bounds__(256) void dec_embed_kernel(const long long* __restr
     for (int e = threadIdx.x; e < E; e += 256) x[(long)b * E + e] = table[id * E + e] + pos_rows[p * E + e];
 }
 
+// dec_embed_kernel for `groups` copies of the batch (the guided ART-V sampler: the drawn token enters the tower on the conditional row
+// b and on the unconditional row B + b): x[(g * B + b), :] for every g, record written once per b.  blockIdx.y = g; the sums are the
+// same two loads and one add per element, so every group holds the bytes dec_embed_kernel writes.
+__global__ __launch_bounds__(256) void dec_embed_groups_kernel(const long long* __restrict__ tok, const float* __restrict__ table,
+                                                               long table_rows, const float* __restrict__ pos_rows,
+                                                               const int* __restrict__ pos_dev, int pos_off, int B, int E,
+                                                               float* __restrict__ x, long long* __restrict__ record, long record_ld,
+                                                               int record_pos0) {
+    const int b = blockIdx.x, g = blockIdx.y;
+    long long id = tok[b];
+    if (record && g == 0 && threadIdx.x == 0 && *pos_dev >= record_pos0 && *pos_dev - record_pos0 < record_ld)
+        record[b * record_ld + (*pos_dev - record_pos0)] = id;
+    if (id < 0 || id >= table_rows) id = 0;
+    const long p = (long)(*pos_dev) + pos_off;
+    float* row = x + ((long)g * B + b) * E;
+    for (int e = threadIdx.x; e < E; e += 256) row[e] = table[id * E + e] + pos_rows[p * E + e];
+}
+
 int gemv_launch(GemvArgs a, hipStream_t s) {
     const bool wide = a.NB > 8;  // 9-16 rows: bf16-exact staged rows only (96 KiB of LDS at 16 x 3,072)
     if (a.NB > GV_MAXB || a.K % 8 != 0 || (long)a.NB * a.K * (a.round_in ? 2 : 4) > 24576 * 4 || (wide && !a.round_in) || a.K > 3072 ||
@@ -914,6 +932,18 @@ extern "C" int mmvid_decode_embed_record(const int64_t* tok, const float* table,
     hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, (const long long*)tok, table, (long)table_rows,
                        pos_rows, pos_dev, pos_off, E, x, (long long*)record, (long)record_ld, record_pos0);
     MMVID_LAUNCH_CHECK("decode_embed");
+    return MMVID_OK;
+}
+
+// ... for x [groups * B, E]: x[g * B + b] = the row of tok[b] for every g < groups (record still [B][record_ld], written once per b)
+extern "C" int mmvid_decode_embed_record_groups(const int64_t* tok, const float* table, int64_t table_rows, const float* pos_rows,
+                                                const int32_t* pos_dev, int pos_off, int B, int groups, int E, float* x, int64_t* record,
+                                                int64_t record_ld, int record_pos0, void* stream) {
+    MMVID_REQUIRE(tok && table && pos_rows && pos_dev && x && B > 0, "decode_embed_groups: bad arguments");
+    MMVID_REQUIRE(groups >= 1 && groups <= 65535, "decode_embed_groups: groups=%d is outside [1, 65535]", groups);
+    hipLaunchKernelGGL(dec_embed_groups_kernel, dim3(B, groups), dim3(256), 0, (hipStream_t)stream, (const long long*)tok, table,
+                       (long)table_rows, pos_rows, pos_dev, pos_off, B, E, x, (long long*)record, (long)record_ld, record_pos0);
+    MMVID_LAUNCH_CHECK("decode_embed_groups");
     return MMVID_OK;
 }
 

@@ -153,6 +153,73 @@ __global__ __launch_bounds__(256) void sample_race_row_kernel(const float* __res
     }
 }
 
+// sample_race_row_kernel on the guided value (the ART-V draw under classifier-free guidance): `logits` is the conditional branch, logits_u
+// (same ld) the unconditional one, row r takes w from scale_dev[r / rows_per_scale].  The value of class c is guided_logit(lc, lu, w), then
+// the same product with inv_temp_div, the same keys, the same (key, index) order: the token is sample_race_kernel<true>'s without noise,
+// bit for bit.  A kernel of its own rather than a template of the one above, which stays the production draw instruction for instruction;
+// eight classes per thread and trip, so sixteen logit requests in flight.
+__global__ __launch_bounds__(256) void sample_race_guided_row_kernel(const float* __restrict__ logits, const float* __restrict__ logits_u,
+                                                                     long ld, const float* __restrict__ scale_dev, long rows_per_scale,
+                                                                     const float* __restrict__ E, const int* __restrict__ step_dev,
+                                                                     int step0, long e_step_stride, float inv_temp_div, int V,
+                                                                     long long tok_offset, long long* __restrict__ tok_out) {
+// (the product with inv_temp_div is rounded before the maximum is subtracted, in both passes, as the wave-per-row kernel does it: left to
+// itself the compiler contracts the second pass's product and subtraction into one operation, and a key moves by an ulp)
+#pragma clang fp contract(off)
+    __shared__ float smx[4];
+    __shared__ Best sb[4];
+    const long r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* x = logits + r * ld;
+    const float* xu = logits_u + r * ld;
+    const float w = scale_dev[r / rows_per_scale];
+    const float* e = E + (step_dev ? (long)(*step_dev - step0) * e_step_stride : 0) + r * (long)V;
+    float mx = -INFINITY;
+    for (int c0 = tid; c0 < V; c0 += 256 * 8) {
+        float xc[8], xn[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool on = c0 + 256 * i < V;
+            xc[i] = on ? x[c0 + 256 * i] : -INFINITY, xn[i] = on ? xu[c0 + 256 * i] : 0.f;  // (a slot past V: lc == -inf stays -inf)
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) mx = fmaxf(mx, guided_logit(xc[i], xn[i], w) * inv_temp_div);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) smx[wave] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(smx[0], smx[1]), fmaxf(smx[2], smx[3]));
+    Best b = {INFINITY, 0x7fffffff};
+    for (int c0 = tid; c0 < V; c0 += 256 * 8) {
+        float xc[8], xn[8], ev[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool on = c0 + 256 * i < V;
+            xc[i] = on ? x[c0 + 256 * i] : -INFINITY, xn[i] = on ? xu[c0 + 256 * i] : 0.f, ev[i] = on ? e[c0 + 256 * i] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (c0 + 256 * i >= V) continue;
+            const float xv = guided_logit(xc[i], xn[i], w) * inv_temp_div;
+            const float p = expf(xv - mx);
+            b = better(b, Best{p > 0.f ? ev[i] / p : INFINITY, c0 + 256 * i});
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        Best ob;
+        ob.key = __shfl_xor(b.key, o, 64);
+        ob.idx = __shfl_xor(b.idx, o, 64);
+        b = better(b, ob);
+    }
+    if (lane == 0) sb[wave] = b;
+    __syncthreads();
+    if (tid == 0) {
+        b = better(better(sb[0], sb[1]), better(sb[2], sb[3]));
+        tok_out[r] = (long long)(b.idx < V ? b.idx : 0) + tok_offset;
+    }
+}
+
 // ---- top-k / nucleus truncation (the rule is in the header comment).  One wave per row, the row in registers: class lane + 64 i is
 // slot i of its lane, NS = ceil(V / 64) rounded up to 4, 16 or 32 slots.  Both edges are found by a 32-step bitwise search over the
 // order-preserving key of g (larger value = larger key):
@@ -650,6 +717,24 @@ extern "C" int mmvid_sample_race_guided(const float* logits_c, const float* logi
                        scale_dev, (long)rows_per_scale, E, noise_u, temperature, 1.0f / logit_div, (long)R, V, (long long)tok_offset,
                        (long long*)tok, y);
     MMVID_LAUNCH_CHECK("sample_race_guided");
+    return MMVID_OK;
+}
+
+// The token-only, block-per-row draw of mmvid_sample_race_at on the guided value (the ART-V token loop under guidance): E is block
+// (*step_dev - step0) of [draws][R][V], or the [R][V] block itself with step_dev == null.  Every refusal comes before the launch.
+extern "C" int mmvid_sample_race_guided_at(const float* logits_c, const float* logits_u, int64_t ld, const float* scale_dev,
+                                           int64_t rows_per_scale, const float* E, const int32_t* step_dev, int step0, int64_t e_step_stride,
+                                           float logit_div, int64_t R, int V, int64_t tok_offset, int64_t* tok, void* stream) {
+    MMVID_REQUIRE(logits_c && logits_u && scale_dev && E && tok && R >= 0 && V > 0 && ld >= V, "sample_race_guided_at: bad arguments");
+    MMVID_REQUIRE(R <= 1024, "sample_race_guided_at: R=%ld rows (one block per row: R <= 1024)", (long)R);
+    MMVID_REQUIRE(logit_div > 0.f, "sample_race_guided_at: logit_div (the softmax temperature divisor) must be > 0");
+    MMVID_REQUIRE(rows_per_scale > 0 && R % rows_per_scale == 0, "sample_race_guided_at: R=%ld is no multiple of rows_per_scale=%ld", (long)R,
+                  (long)rows_per_scale);
+    if (R == 0) return MMVID_OK;
+    hipLaunchKernelGGL(sample_race_guided_row_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, logits_c, logits_u, (long)ld,
+                       scale_dev, (long)rows_per_scale, E, step_dev, step0, (long)e_step_stride, 1.0f / logit_div, V, (long long)tok_offset,
+                       (long long*)tok);
+    MMVID_LAUNCH_CHECK("sample_race_guided_at");
     return MMVID_OK;
 }
 

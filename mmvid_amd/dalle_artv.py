@@ -9,6 +9,7 @@ materialised: each of the three position segments runs `to_logits` against ITS b
 MFMA GEMM + the fused cross-entropy kernels), which is the same loss with ~14x fewer head FLOPs and no [B, L, 51584]
 tensors.  Sampling keeps a per-layer key/value cache (the reference recomputes the whole prefix per token) and draws
 tokens with the device sampler of csrc/sample.hip."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -17,9 +18,10 @@ from . import artv_sampling, ops, sampling
 from .artv_sampling import k_keep, keep_top
 from .clip_tower import OpenAICLIPTransformer
 from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
-from .frontend import Frontend, face_choices
+from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import AssembleSequence, LNLinear, LNLinearCrossEntropy
 from .modules import AxialPositionalEmbedding, AxialPositionalEmbeddingList
+from .sampling import GUIDANCE_DROPS
 
 NEG = -torch.finfo(torch.float32).max
 
@@ -240,8 +242,17 @@ class DALLE(nn.Module):
             return ops.gemm(hn, self._w16()[cols[0]:cols[1]], bias=lin.bias.detach()[cols[0]:cols[1]], out_dtype=torch.float32)
 
     def forward(self, text, visual=None, target=None, return_loss=False, erase_visual=False, erase_visual_half=False,
-                vc_mode=None, face_mode=None, visual_aug_mode=None, **kwargs):
+                vc_mode=None, face_mode=None, visual_aug_mode=None, null_text_prob=0.0, null_visual_prob=0.0, _null=None, **kwargs):
+        """`null_text_prob` / `null_visual_prob` (training for classifier-free guidance): each sample's text becomes all pad and its visual
+        control all pad ids (what an empty text and visual=None give that sample) with these probabilities, drawn on the device before the
+        ids are built (Frontend.cond_drop); the labels of the text and visual segments are the ids after the drop.  `_null` (uint8 [B, 2])
+        injects the decisions (tests).  A forward with the drop on advances the front-end's call counter at its end, so the next step
+        draws new decisions; both probabilities 0 and no `_null`: nothing is launched and the counter stays."""
+        drop = check_condition_drop(null_text_prob, null_visual_prob, False, return_loss, _null is not None)
         vis_tok = self._visual_tokens(visual, erase_visual, erase_visual_half, vc_mode, face_mode, visual_aug_mode)
+        if drop:
+            text, vis_tok = self.frontend.cond_drop(text.contiguous(), vis_tok.contiguous() if vis_tok is not None else None, null_text_prob,
+                                                    null_visual_prob, -1, _null)
         out, text, visual, image = self._hidden(text, vis_tok, target)
         B, L, E = out.shape
         if not return_loss:
@@ -263,6 +274,8 @@ class DALLE(nn.Module):
         loss = (losses[0] + self.loss_vis_weight * losses[1] + self.loss_img_weight * losses[2]) / \
             (self.loss_img_weight + self.loss_vis_weight + 1)
         zero = torch.tensor(0.0, device=text.device)
+        if drop:
+            self.frontend.advance(text.device)
         return loss, zero, zero
 
     # ---- sampling ---------------------------------------------------------------------------------------------------------
@@ -282,21 +295,77 @@ class DALLE(nn.Module):
         k, p = trunc[0][0], trunc[1][0]
         return (k, p) if (k is not None and k < V) or (p is not None and p < 1.0) else None
 
-    def _draw(self, block_logits, filter_thres, temperature, race, name, trunc=None):
+    def _guidance(self, B, guidance_scale, guidance_drop, negative_text, filter_thres):
+        """generate_images' guidance keywords (sampling.check_guidance and the rules of the token loop, before any device work) ->
+        (drop, scale), or None for the unguided call.  scale: a float, or a tensor [B] with one scale per video."""
+        drop = sampling.check_guidance(self.num_visuals, False, guidance_scale, guidance_drop, negative_text)
+        if drop is None:
+            return None
+        if isinstance(guidance_scale, (list, tuple, np.ndarray)) or (torch.is_tensor(guidance_scale) and guidance_scale.dim() > 1):
+            raise ValueError('guidance_scale: a per-token schedule (a sequence, or a tensor [steps, B]) is not accepted: the captured token '
+                             f'step reads one scale per video; pass a float or a tensor [B] = [{B}]')
+        if torch.is_tensor(guidance_scale):
+            if guidance_scale.dim() == 1 and guidance_scale.shape[0] != B:
+                raise ValueError(f'guidance_scale: a tensor must be [B] = [{B}] (one scale per video), got {tuple(guidance_scale.shape)}')
+            scale = guidance_scale.detach().to(torch.float32).expand(B)
+            finite = scale.is_cuda or bool(torch.isfinite(scale).all())  # (a tensor already on the device is not read back)
+        else:
+            try:
+                scale = float(guidance_scale)
+            except (TypeError, ValueError):
+                raise ValueError(f'guidance_scale: expected a float or a tensor [{B}], got {type(guidance_scale).__name__}') from None
+            finite = np.isfinite(scale)
+        if not finite:
+            raise ValueError('guidance_scale: every scale must be finite')
+        if negative_text is not None and (not torch.is_tensor(negative_text) or negative_text.dim() != 2 or
+                                          tuple(negative_text[:, :self.text_seq_len].shape) != (B, self.text_seq_len)):
+            got = tuple(negative_text.shape) if torch.is_tensor(negative_text) else type(negative_text).__name__
+            raise ValueError(f'negative_text: expected int64 [B, text_seq_len] = [{B}, {self.text_seq_len}], got {got}')
+        if k_keep(filter_thres, self.total_tokens) < self.num_image_tokens:
+            raise ValueError(f'guidance_scale with filter_thres = {filter_thres}, which removes image classes: the torch.topk filter has no '
+                             'guided form; leave filter_thres where it keeps the block and truncate with top_k (or top_p)')
+        return drop, scale
+
+    @staticmethod
+    def _scale_vector(scale, B, device):
+        """-> fp32 [B] on the device: what the guided kernels read."""
+        if torch.is_tensor(scale):
+            return scale.to(device=device, dtype=torch.float32).expand(B).contiguous()
+        return torch.full((B, ), float(scale), dtype=torch.float32, device=device)
+
+    def _draw(self, block_logits, filter_thres, temperature, race, name, trunc=None, logits_u=None, scale=None):
         """One token per row from the logits of the position's class block (dalle_artv.py:274-276): top_k over ALL
         total_tokens classes keeps k = int((1 - thres) * total_tokens) of them; the classes outside the block sit at -max,
-        so the filter only ever removes block classes when k is smaller than the block."""
+        so the filter only ever removes block classes when k is smaller than the block.  logits_u (same row stride) with scale (fp32
+        [B] on the device): the draw is on block_logits + w * (block_logits - logits_u); filter_thres keeps the block then."""
         B, n = block_logits.shape
-        block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens)).contiguous()
-        if trunc is not None:  # top-k / nucleus of what filter_thres left (ops.logits_truncate)
-            block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logit_div=temperature)
+        if logits_u is None:
+            block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens)).contiguous()
+            if trunc is not None:  # top-k / nucleus of what filter_thres left (ops.logits_truncate)
+                block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logit_div=temperature)
+        elif trunc is not None:  # the guided value, truncated: the plain draw follows
+            block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logits_u=logits_u, scale=scale, rows_per_scale=1,
+                                               logit_div=temperature)
+            logits_u = None
         E = race(name, (B, n)) if race is not None else ops.exponential_like((B, n), block_logits.device)
+        if logits_u is not None:
+            return ops.sample_race_guided_at(block_logits, logits_u, scale, 1, E, logit_div=temperature).view(B, 1)
         tok, _ = ops.sample_race(block_logits, E, None, 0.0, logit_div=temperature, want_y=False)
         return tok.view(B, 1)
 
-    def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None):
-        """The probability vector `_draw` samples from (tests compare it with the reference's full-width expression)."""
+    def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None, logits_u=None, guidance_scale=None):
+        """The probability vector `_draw` samples from (tests compare it with the reference's full-width expression); with logits_u and
+        guidance_scale, of the guided, then truncated, value."""
         trunc = self._truncation(top_k, top_p, block_logits.shape[1])
+        if (logits_u is None) != (guidance_scale is None):
+            raise ValueError('sampling_probs: logits_u and guidance_scale come together')
+        if logits_u is not None:
+            B = block_logits.shape[0]
+            _, scale = self._guidance(B, guidance_scale, GUIDANCE_DROPS, None, filter_thres)
+            k, p = trunc if trunc is not None else (None, None)  # (both filters off: the guided value is copied through)
+            block_logits = ops.logits_truncate(block_logits.contiguous(), k, p, logits_u=logits_u.contiguous(),
+                                               scale=self._scale_vector(scale, B, block_logits.device), rows_per_scale=1, logit_div=temperature)
+            return F.softmax(block_logits / temperature, dim=-1)
         block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens))
         if trunc is not None:
             block_logits = ops.logits_truncate(block_logits.contiguous(), trunc[0], trunc[1], logit_div=temperature)
@@ -305,37 +374,60 @@ class DALLE(nn.Module):
     @torch.no_grad()
     @eval_decorator
     def generate_images(self, text, *, clip=None, visual=None, mask=None, filter_thres=0.5, temperature=1.,
-                        erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, _race=None, **kwargs):
+                        erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None,
+                        guidance_drop=GUIDANCE_DROPS, negative_text=None, _race=None, _trace=None, **kwargs):
         """dalle_artv.py:236-304.  use_cache=True (default): the prompt runs once and every sampled token costs one
         incremental step over the per-layer key/value cache; use_cache=False: the reference's algorithm (the whole
         transformer over the growing prefix per token).  Both draw from the same distribution: softmax over the image
         block of the last position's logits (tests/test_parity_gpu.py compares it with the reference's expression).
         `top_k` (an int) / `top_p` (a float in (0, 1]) truncate that distribution, after whatever `filter_thres` did, to its k most
         likely classes / to its nucleus of mass top_p, with defined ties (ops.logits_truncate): one more launch per token, captured
-        with the step."""
-        trunc = self._truncation(top_k, top_p, self.num_image_tokens)
+        with the step.
+
+        `guidance_scale` (a finite float, or a tensor [B] with one scale per video; None: the unguided call) switches classifier-free
+        guidance on: every token is drawn from lc + w * (lc - lu), lu the logits under an unconditional prompt that runs beside the
+        conditional one as rows B..2B-1 of the same prefill, cache and decode step and receives the same drawn tokens.  That prompt
+        lacks what `guidance_drop` names ('text': all pad; 'visual': every slot its pad id) and takes `negative_text` (int64
+        [B, text_seq_len]) for its text when given.  top_k / top_p then truncate the guided distribution.  Not accepted with guidance: a
+        per-token scale schedule, and a `filter_thres` that removes image classes.  `_trace` (a list, cached path): one dict of clones
+        per token (artv_sampling.sample), through the eager loop with per-token variates."""
         tsl = self.text_seq_len
         text = text[:, :tsl]
         B = text.shape[0]
+        guide = self._guidance(B, guidance_scale, guidance_drop, negative_text, filter_thres)
+        trunc = self._truncation(top_k, top_p, self.num_image_tokens)
+        if _trace is not None and not use_cache:
+            raise ValueError('_trace records the token loop over the key/value cache: use_cache=True')
         # visual control tokens (with the erasing the reference applies on every step, dalle_artv.py:464-472) are fixed
         # during sampling: tokenise once
         vis_tok = self._visual_tokens(visual, erase_visual, True, vc_mode, face_mode, None)
         cl = self.control_seq_len
         c0, c1 = self._allowed_range(cl)
+        scale = None
+        if guide is not None:  # rows B..2B-1: the unconditional prompt (both branches share the erase and the face region of vis_tok)
+            drop, scale = guide[0], self._scale_vector(guide[1], B, text.device)
+            text_u = negative_text[:, :tsl].to(text.device) if negative_text is not None else (torch.zeros_like(text) if 'text' in drop else text)
+            vis_u = None if 'visual' in drop else vis_tok
+            if vis_tok is not None and vis_u is None:
+                vis_u = torch.full_like(vis_tok, -1)
+            text, vis_tok = torch.cat((text, text_u), 0), (torch.cat((vis_tok, vis_u), 0) if vis_tok is not None else None)
+        rows = text.shape[0]
         toks = []
         if use_cache:
-            cache = self.transformer.new_kv_cache(B, self.total_seq_len, text.device)
+            cache = self.transformer.new_kv_cache(rows, self.total_seq_len, text.device)
             prompt = torch.cat(self._prompt_ids(text, vis_tok), 1)  # <bos> text visual: positions 0 .. cl
             h = self.transformer.prefill(self._embed_rows(prompt, 0), cache)[:, -1, :].contiguous()
-            toks = artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc)
+            toks = artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc, scale, _trace)
         else:
-            image = torch.empty(B, 0, dtype=torch.long, device=text.device)
+            image = torch.empty(rows, 0, dtype=torch.long, device=text.device)
             for step in range(self.target_seq_len):
                 hidden = self._hidden(text, vis_tok, image)[0]
-                sample = self._draw(self._logits_rows(hidden[:, -1, :].contiguous(), (c0, c1)), filter_thres, temperature,
-                                    _race, f'tok{step}', trunc)
+                logits = self._logits_rows(hidden[:, -1, :].contiguous(), (c0, c1))
+                sample = self._draw(logits[:B], filter_thres, temperature, _race, f'tok{step}', trunc, logits[B:] if guide is not None else None,
+                                    scale)
                 toks.append(sample)
-                image = torch.cat((image, sample), dim=-1)
+                image = torch.cat((image, sample if guide is None else sample.repeat(2, 1)), dim=-1)  # (both halves carry the same tokens)
+        text = text[:B]
         img_seq = torch.cat(toks, dim=-1).reshape(-1, self.image_seq_len)
         images = self.vae.decode(img_seq)
         if self.num_targets > 1:

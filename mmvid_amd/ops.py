@@ -654,6 +654,30 @@ def sample_race_guided(logits_c, logits_u, scale, rows_per_scale, E, noise_u=Non
     return tok, y
 
 
+def sample_race_guided_at(logits_c, logits_u, scale, rows_per_scale, E, logit_div=1.0, tok_offset=0, tok_out=None, step_dev=None, step0=0):
+    """The token-only draw of sample_race (want_y False, no noise; R <= 1024) on the guided value of sample_race_guided: logits_c, logits_u
+    [R, V] f32 with one row stride, scale f32 [R // rows_per_scale] on the device, E [R, V], or [draws, R, V] with step_dev (int32 device
+    scalar: draw number step_dev - step0 is used) -> tok int64 [R] (tok_out if given)."""
+    _chk(E, f32, 'E'), _chk(scale, f32, 'scale')
+    assert logits_c.dtype == f32 and logits_c.is_cuda and logits_c.stride(1) == 1
+    assert logits_u.dtype == f32 and logits_u.is_cuda and logits_u.stride(1) == 1
+    R, V = logits_c.shape
+    if tuple(logits_u.shape) != (R, V) or logits_u.stride(0) != logits_c.stride(0):
+        raise ValueError(f'sample_race_guided_at: logits_u {tuple(logits_u.shape)} (row stride {logits_u.stride(0)}) must have the shape '
+                         f'and the row stride of logits_c {(R, V)} ({logits_c.stride(0)})')
+    assert E.shape[-2:] == (R, V) and E.is_contiguous() and (E.dim() == 2 or (E.dim() == 3 and step_dev is not None))
+    rows_per_scale = int(rows_per_scale)
+    if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
+        raise ValueError(f'sample_race_guided_at: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
+    if tok_out is not None:
+        _chk(tok_out, i64, 'tok_out')
+        assert tok_out.shape == (R, )
+    tok = tok_out if tok_out is not None else torch.empty(R, device=logits_c.device, dtype=i64)
+    call('mmvid_sample_race_guided_at', _p(logits_c), _p(logits_u), logits_c.stride(0), _p(scale), rows_per_scale, _p(E),
+         _p(step_dev) if step_dev is not None else None, int(step0), R * V, float(logit_div), R, V, int(tok_offset), _p(tok), _stream())
+    return tok
+
+
 def logits_truncate(logits, top_k=None, top_p=None, *, logits_u=None, scale=None, rows_per_scale=None, logit_div=1.0, out=None,
                     want_kept=False):
     """Top-k / nucleus truncation of logits [R, V] f32 (row stride = logits.stride(0), V <= 2048) -> out [R, V] (`out` if given; it may
@@ -798,5 +822,21 @@ def decode_embed(tok, table, pos_rows, pos_dev, out, pos_off=0, record=None, rec
         _chk(record, i64, 'record')
         assert record.shape[0] == B and record.stride(1) == 1
     call('mmvid_decode_embed_record', _p(tok), _p(table), table.shape[0], _p(pos_rows), _p(pos_dev), int(pos_off), B, E, _p(out),
+         _p(record) if record is not None else None, record.stride(0) if record is not None else 0, int(record_pos0), _stream())
+    return out
+
+
+def decode_embed_groups(tok, table, pos_rows, pos_dev, out, groups, pos_off=0, record=None, record_pos0=0):
+    """decode_embed for `groups` copies of the batch: tok [B], out [groups * B, E], out[g * B + b] = table[tok[b]] + pos_rows[pos_dev + pos_off]
+    for every g (the guided ART-V sampler's two tower rows per video); record (int64 [B, n], optional) is written once per b."""
+    _chk(tok, i64, 'tok'), _chk(table, f32, 'table'), _chk(pos_rows, f32, 'pos_rows'), _chk(out, f32, 'out')
+    B, groups = tok.shape[0], int(groups)
+    if groups < 1 or out.dim() != 2 or out.shape[0] != groups * B:
+        raise ValueError(f'decode_embed_groups: out {tuple(out.shape)} is not [groups * B, E] = [{groups} * {B}, E]')
+    E = out.shape[1]
+    if record is not None:
+        _chk(record, i64, 'record')
+        assert record.shape[0] == B and record.stride(1) == 1
+    call('mmvid_decode_embed_record_groups', _p(tok), _p(table), table.shape[0], _p(pos_rows), _p(pos_dev), int(pos_off), B, groups, E, _p(out),
          _p(record) if record is not None else None, record.stride(0) if record is not None else 0, int(record_pos0), _stream())
     return out
