@@ -8,7 +8,9 @@
  *   - return 0 on success; otherwise an error code, message via mmvid_last_error() (per host thread);
  *   - bf16 buffers are raw uint16 bit patterns (`void*` here), fp32 accumulation everywhere;
  *   - "ld*" are leading dimensions in ELEMENTS.
- * The Python binding is mmvid_amd/_lib.py (ctypes); INTEGRATION.md shows the reference-side call sites.
+ * The Python binding (mmvid_amd/_lib.py, ctypes) is derived from THIS FILE by mmvid_amd/_cdecl.py, a strict reader of the plain
+ * declaration forms used below: a form it does not know is an import error, not a guess.  INTEGRATION.md shows the reference-side
+ * call sites.
  */
 #ifndef MMVID_HIP_H
 #define MMVID_HIP_H
@@ -16,6 +18,10 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* What mmvid_abi_version() returns.  It changes when an existing entry point or struct changes (added ones leave it); the Python
+ * binding reads it from here and refuses a library built from another value. */
+#define MMVID_ABI_VERSION 3
 
 const char* mmvid_last_error(void);
 int mmvid_abi_version(void);

@@ -4,6 +4,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from ._cdecl import HEADER_PATH
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, '_obj')
@@ -14,7 +16,7 @@ FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-res
 
 def _deps_mtime():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
-    hs.append(os.path.join(os.path.dirname(HERE), 'include', 'mmvid_hip.h'))
+    hs.append(HEADER_PATH)
     return max(os.path.getmtime(h) for h in hs)
 
 

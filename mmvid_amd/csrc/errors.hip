@@ -2,6 +2,7 @@
 // kept per host thread and read back with mmvid_last_error().
 #include <stdarg.h>
 
+#include "../../include/mmvid_hip.h"
 #include "common.h"
 
 static thread_local char g_err[512] = "";
@@ -16,7 +17,7 @@ void mmvid_set_error(const char* fmt, ...) {
 extern "C" const char* mmvid_last_error() { return g_err; }
 
 // 2: the front-end state buffer grew from one float (the step counter) to four 32-bit words {step, seed lo, seed hi, reserved}
-extern "C" int mmvid_abi_version() { return 3; }
+extern "C" int mmvid_abi_version() { return MMVID_ABI_VERSION; }
 
 // Number of visible HIP devices (0 when none) -- lets the host side fail loudly and early.
 extern "C" int mmvid_device_count() {
