@@ -8,14 +8,14 @@ persistent launch, with a restart point from which launch_loop finishes the call
 
 Classifier-free guidance (`guide`: one fp32 scale per video, on the device): the cache, the session and the head rows hold 2B sequences,
 rows 0..B-1 under the conditional prompt and rows B..2B-1 under the unconditional one.  One head launch gives both logit blocks, the
-draw races lc + w * (lc - lu) (mmvid_sample_race_guided_at, or the guided truncation followed by the plain draw), and the embedding
-launch writes the drawn token's row for both halves: the launches of a guided token are the unguided token's, and launch_loop
-captures them the same way.  A guided call never takes token_launch_loop."""
+draw races lc + w * (lc - lu), and the embedding launch writes the drawn token's row for both halves: the launches of a guided token
+are the unguided token's, and launch_loop captures them the same way.  A guided call never takes token_launch_loop.  Which launches
+make a draw (plain, truncated, guided, both) is token_draw.draw's decision; TokenLoop.draw hands it the static buffers."""
 import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, token_draw
 
 
 def k_keep(filter_thres, total):
@@ -53,6 +53,8 @@ class TokenLoop:
         # the KV cache (batch 64 at 1,024 steps x 1,024 codes) and at the 1,024 rows the indexed draw kernel takes: larger calls draw per step
         fits = race is None and trace is None and self.steps * B * self.V <= (1 << 26) and B <= 1024
         self.E_all = torch.empty(self.steps, B, self.V, device=dev).exponential_() if fits else None
+        self.guided = dict(logits_u=self.lu, scale=guide, rows_per_scale=1) if guide is not None else {}  # (built once: draw runs per token)
+        self.variates = (self.E_all, dict(step_dev=self.sess.pos, step0=first_pos)) if fits else (self.E, {})
         self.hid = self.hbuf  # the hidden state the next draw reads: the prompt's last position, then the session's output buffer
 
     def draw(self, step):
@@ -68,29 +70,14 @@ class TokenLoop:
         ops.gemv_rows(src, self.w_blk, self.b_blk, ln=(ln.weight, ln.bias, ln.eps), round_in=True, out=self.logits)  # LN + head block
         if rec is not None:
             rec['logits'] = self.logits.clone()
-        lg = None  # what the plain draw reads; None: the guided draw reads both branches
-        if self.guide is None:
-            lg = keep_top(self.logits, self.k_keep)
-            if self.trunc is not None:
-                lg = ops.logits_truncate(lg, self.trunc[0], self.trunc[1], logit_div=T, out=lg, want_kept=rec is not None)
-        elif self.trunc is not None:  # the nucleus is the guided distribution's; what it leaves goes through the plain draw
-            lg = ops.logits_truncate(self.lc, self.trunc[0], self.trunc[1], logits_u=self.lu, scale=self.guide, rows_per_scale=1, logit_div=T,
-                                     out=self.lt, want_kept=rec is not None)
-        if rec is not None and self.trunc is not None:
-            lg, rec['kept'] = lg
-            rec['logits_t'] = lg.clone()
-        if self.E_all is not None:
-            E, at = self.E_all, dict(step_dev=self.sess.pos, step0=self.first_pos)
-        else:
-            E, at = self.E, {}
-            if self.race is not None:
-                E.copy_(self.race(f'tok{step}', tuple(E.shape)))
-            else:
-                E.exponential_()
-        if lg is None:
-            ops.sample_race_guided_at(self.lc, self.lu, self.guide, 1, E, logit_div=T, tok_out=self.tok, **at)
-        else:
-            ops.sample_race(lg, E, None, 0.0, logit_div=T, want_y=False, tok_out=self.tok, **at)
+        lg = keep_top(self.logits, self.k_keep) if self.guide is None else self.lc
+        E, at = self.variates
+        if self.race is not None:
+            E.copy_(self.race(f'tok{step}', tuple(E.shape)))
+        elif self.E_all is None:
+            E.exponential_()
+        token_draw.draw(lg, E, trunc=self.trunc, logit_div=T, want_y=False, tok_out=self.tok, record=rec, **self.guided, **at,
+                        trunc_out=lg if self.guide is None else self.lt)  # unguided: the truncation is in place
         if rec is not None:
             rec['E'], rec['tok'] = E.clone(), self.tok.clone()
             if self.guide is not None:

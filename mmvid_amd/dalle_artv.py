@@ -9,19 +9,17 @@ materialised: each of the three position segments runs `to_logits` against ITS b
 MFMA GEMM + the fused cross-entropy kernels), which is the same loss with ~14x fewer head FLOPs and no [B, L, 51584]
 tensors.  Sampling keeps a per-layer key/value cache (the reference recomputes the whole prefix per token) and draws
 tokens with the device sampler of csrc/sample.hip."""
-import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import artv_sampling, ops, sampling
+from . import artv_sampling, ops, sampling, token_draw
 from .artv_sampling import k_keep, keep_top
 from .clip_tower import OpenAICLIPTransformer
 from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
 from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import AssembleSequence, LNLinear, LNLinearCrossEntropy
 from .modules import AxialPositionalEmbedding, AxialPositionalEmbeddingList
-from .sampling import GUIDANCE_DROPS
 
 NEG = -torch.finfo(torch.float32).max
 
@@ -286,96 +284,43 @@ class DALLE(nn.Module):
                                      self._seg[first_pos:first_pos + n].contiguous(),
                                      self._pos_rows()[first_pos:first_pos + n].contiguous())
 
-    def _truncation(self, top_k, top_p, V):
-        """generate_images' `top_k` / `top_p` (scalars; sampling.check_truncation, before any device work) -> (k | None, p | None), or
-        None when neither can remove a class of the V-class image block."""
-        trunc = sampling.check_truncation(top_k, top_p, 1, V)
-        if trunc is None:
-            return None
-        k, p = trunc[0][0], trunc[1][0]
-        return (k, p) if (k is not None and k < V) or (p is not None and p < 1.0) else None
-
     def _guidance(self, B, guidance_scale, guidance_drop, negative_text, filter_thres):
-        """generate_images' guidance keywords (sampling.check_guidance and the rules of the token loop, before any device work) ->
-        (drop, scale), or None for the unguided call.  scale: a float, or a tensor [B] with one scale per video."""
-        drop = sampling.check_guidance(self.num_visuals, False, guidance_scale, guidance_drop, negative_text)
-        if drop is None:
-            return None
-        if isinstance(guidance_scale, (list, tuple, np.ndarray)) or (torch.is_tensor(guidance_scale) and guidance_scale.dim() > 1):
-            raise ValueError('guidance_scale: a per-token schedule (a sequence, or a tensor [steps, B]) is not accepted: the captured token '
-                             f'step reads one scale per video; pass a float or a tensor [B] = [{B}]')
-        if torch.is_tensor(guidance_scale):
-            if guidance_scale.dim() == 1 and guidance_scale.shape[0] != B:
-                raise ValueError(f'guidance_scale: a tensor must be [B] = [{B}] (one scale per video), got {tuple(guidance_scale.shape)}')
-            scale = guidance_scale.detach().to(torch.float32).expand(B)
-            finite = scale.is_cuda or bool(torch.isfinite(scale).all())  # (a tensor already on the device is not read back)
-        else:
-            try:
-                scale = float(guidance_scale)
-            except (TypeError, ValueError):
-                raise ValueError(f'guidance_scale: expected a float or a tensor [{B}], got {type(guidance_scale).__name__}') from None
-            finite = np.isfinite(scale)
-        if not finite:
-            raise ValueError('guidance_scale: every scale must be finite')
-        if negative_text is not None and (not torch.is_tensor(negative_text) or negative_text.dim() != 2 or
-                                          tuple(negative_text[:, :self.text_seq_len].shape) != (B, self.text_seq_len)):
-            got = tuple(negative_text.shape) if torch.is_tensor(negative_text) else type(negative_text).__name__
-            raise ValueError(f'negative_text: expected int64 [B, text_seq_len] = [{B}, {self.text_seq_len}], got {got}')
-        if k_keep(filter_thres, self.total_tokens) < self.num_image_tokens:
-            raise ValueError(f'guidance_scale with filter_thres = {filter_thres}, which removes image classes: the torch.topk filter has no '
-                             'guided form; leave filter_thres where it keeps the block and truncate with top_k (or top_p)')
-        return drop, scale
+        return sampling.check_guidance_artv(self.num_visuals, self.text_seq_len, self.total_tokens, self.num_image_tokens, B, guidance_scale,
+                                            guidance_drop, negative_text, filter_thres)
 
-    @staticmethod
-    def _scale_vector(scale, B, device):
-        """-> fp32 [B] on the device: what the guided kernels read."""
-        if torch.is_tensor(scale):
-            return scale.to(device=device, dtype=torch.float32).expand(B).contiguous()
-        return torch.full((B, ), float(scale), dtype=torch.float32, device=device)
+    _scale_vector = staticmethod(sampling.scale_vector)
 
     def _draw(self, block_logits, filter_thres, temperature, race, name, trunc=None, logits_u=None, scale=None):
-        """One token per row from the logits of the position's class block (dalle_artv.py:274-276): top_k over ALL
-        total_tokens classes keeps k = int((1 - thres) * total_tokens) of them; the classes outside the block sit at -max,
-        so the filter only ever removes block classes when k is smaller than the block.  logits_u (same row stride) with scale (fp32
-        [B] on the device): the draw is on block_logits + w * (block_logits - logits_u); filter_thres keeps the block then."""
+        """One token per row from the logits of the position's class block (dalle_artv.py:274-276): top_k over ALL total_tokens classes keeps
+        k = int((1 - thres) * total_tokens) of them; the classes outside the block sit at -max, so the filter only ever removes block classes
+        when k is smaller than the block.  logits_u (same row stride) with scale (fp32 [B] on the device): the guided draw (token_draw.draw)."""
         B, n = block_logits.shape
         if logits_u is None:
             block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens)).contiguous()
-            if trunc is not None:  # top-k / nucleus of what filter_thres left (ops.logits_truncate)
-                block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logit_div=temperature)
-        elif trunc is not None:  # the guided value, truncated: the plain draw follows
-            block_logits = ops.logits_truncate(block_logits, trunc[0], trunc[1], logits_u=logits_u, scale=scale, rows_per_scale=1,
-                                               logit_div=temperature)
-            logits_u = None
         E = race(name, (B, n)) if race is not None else ops.exponential_like((B, n), block_logits.device)
-        if logits_u is not None:
-            return ops.sample_race_guided_at(block_logits, logits_u, scale, 1, E, logit_div=temperature).view(B, 1)
-        tok, _ = ops.sample_race(block_logits, E, None, 0.0, logit_div=temperature, want_y=False)
-        return tok.view(B, 1)
+        return token_draw.draw(block_logits, E, logits_u=logits_u, scale=scale, rows_per_scale=1, trunc=trunc, logit_div=temperature,
+                               want_y=False)[0].view(B, 1)
 
     def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None, logits_u=None, guidance_scale=None):
         """The probability vector `_draw` samples from (tests compare it with the reference's full-width expression); with logits_u and
-        guidance_scale, of the guided, then truncated, value."""
-        trunc = self._truncation(top_k, top_p, block_logits.shape[1])
+        guidance_scale, of the guided, then truncated, value (both filters off: the guided value is copied through)."""
+        B, guide = block_logits.shape[0], {}
+        trunc = sampling.check_truncation_artv(top_k, top_p, block_logits.shape[1])
         if (logits_u is None) != (guidance_scale is None):
             raise ValueError('sampling_probs: logits_u and guidance_scale come together')
         if logits_u is not None:
-            B = block_logits.shape[0]
-            _, scale = self._guidance(B, guidance_scale, GUIDANCE_DROPS, None, filter_thres)
-            k, p = trunc if trunc is not None else (None, None)  # (both filters off: the guided value is copied through)
-            block_logits = ops.logits_truncate(block_logits.contiguous(), k, p, logits_u=logits_u.contiguous(),
-                                               scale=self._scale_vector(scale, B, block_logits.device), rows_per_scale=1, logit_div=temperature)
-            return F.softmax(block_logits / temperature, dim=-1)
-        block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens))
-        if trunc is not None:
-            block_logits = ops.logits_truncate(block_logits.contiguous(), trunc[0], trunc[1], logit_div=temperature)
-        return F.softmax(block_logits / temperature, dim=-1)
+            scale = self._scale_vector(self._guidance(B, guidance_scale, sampling.GUIDANCE_DROPS, None, filter_thres)[1], B, block_logits.device)
+            guide = dict(logits_u=logits_u.contiguous(), scale=scale, rows_per_scale=1)
+        else:
+            block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens))
+        lg = token_draw.race_value(block_logits.contiguous(), trunc=trunc, logit_div=temperature, materialise=True, **guide)[0]
+        return F.softmax(lg / temperature, dim=-1)
 
     @torch.no_grad()
     @eval_decorator
     def generate_images(self, text, *, clip=None, visual=None, mask=None, filter_thres=0.5, temperature=1.,
                         erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None,
-                        guidance_drop=GUIDANCE_DROPS, negative_text=None, _race=None, _trace=None, **kwargs):
+                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, _race=None, _trace=None, **kwargs):
         """dalle_artv.py:236-304.  use_cache=True (default): the prompt runs once and every sampled token costs one
         incremental step over the per-layer key/value cache; use_cache=False: the reference's algorithm (the whole
         transformer over the growing prefix per token).  Both draw from the same distribution: softmax over the image
@@ -395,7 +340,7 @@ class DALLE(nn.Module):
         text = text[:, :tsl]
         B = text.shape[0]
         guide = self._guidance(B, guidance_scale, guidance_drop, negative_text, filter_thres)
-        trunc = self._truncation(top_k, top_p, self.num_image_tokens)
+        trunc = sampling.check_truncation_artv(top_k, top_p, self.num_image_tokens)
         if _trace is not None and not use_cache:
             raise ValueError('_trace records the token loop over the key/value cache: use_cache=True')
         # visual control tokens (with the erasing the reference applies on every step, dalle_artv.py:464-472) are fixed
@@ -406,8 +351,7 @@ class DALLE(nn.Module):
         scale = None
         if guide is not None:  # rows B..2B-1: the unconditional prompt (both branches share the erase and the face region of vis_tok)
             drop, scale = guide[0], self._scale_vector(guide[1], B, text.device)
-            text_u = negative_text[:, :tsl].to(text.device) if negative_text is not None else (torch.zeros_like(text) if 'text' in drop else text)
-            vis_u = None if 'visual' in drop else vis_tok
+            text_u, vis_u = sampling.unconditional_inputs(text, vis_tok, drop, negative_text[:, :tsl] if negative_text is not None else None)
             if vis_tok is not None and vis_u is None:
                 vis_u = torch.full_like(vis_tok, -1)
             text, vis_tok = torch.cat((text, text_u), 0), (torch.cat((vis_tok, vis_u), 0) if vis_tok is not None else None)

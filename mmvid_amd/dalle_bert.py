@@ -593,18 +593,15 @@ class BERT(nn.Module):
 
     @torch.no_grad()
     def guidance_control(self, text, drop, negative_text=None, *, visual=None, erase_visual=False, vc_mode=None, face_mode=None):
-        """The unconditional control of a guided call: one more control-only forward (the front-end step counter advances once more).
-        Its text is `negative_text` when given, all pad when `drop` names 'text', else `text`; its visual control is None (all [MASK])
-        when `drop` names 'visual', else `visual` with the same erase_visual / vc_mode / face_mode.  `drop`: sampling.check_guidance."""
-        if negative_text is not None:
-            if self.fixed_language_model is None and (tuple(negative_text.shape) != tuple(text.shape) or negative_text.dtype != torch.int64):
-                raise ValueError(f'negative_text: expected int64 {tuple(text.shape)} like text, got {negative_text.dtype} '
-                                 f'{tuple(negative_text.shape)}')
-            text_u = negative_text.to(text.device)
-        else:
-            text_u = torch.zeros_like(text) if 'text' in drop else text
-        return self(text_u, visual=None if 'visual' in drop else visual, erase_visual=erase_visual, erase_visual_half=True,
-                    vc_mode=vc_mode, face_mode=face_mode, return_loss=False)
+        """The unconditional control of a guided call: one more control-only forward (the front-end step counter advances once more) on
+        sampling.unconditional_inputs (visual None: all [MASK]), same erase_visual / vc_mode / face_mode.  `drop`: sampling.check_guidance."""
+        if negative_text is not None and self.fixed_language_model is None and (
+                tuple(negative_text.shape) != tuple(text.shape) or negative_text.dtype != torch.int64):
+            raise ValueError(f'negative_text: expected int64 {tuple(text.shape)} like text, got {negative_text.dtype} '
+                             f'{tuple(negative_text.shape)}')
+        text_u, visual_u = sampling.unconditional_inputs(text, visual, drop, negative_text)
+        return self(text_u, visual=visual_u, erase_visual=erase_visual, erase_visual_half=True, vc_mode=vc_mode, face_mode=face_mode,
+                    return_loss=False)
 
     @torch.no_grad()
     def mask_predict(self, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1,

@@ -631,22 +631,29 @@ def sample_race(logits, E, noise_u=None, temperature=0.0, logit_div=1.0, tok_off
     return tok, y
 
 
+def _guided_operands(name, logits_c, logits_u, scale, rows_per_scale):
+    """The operand checks of the guided form of `name` (one row stride; one f32 scale per rows_per_scale rows) -> (R, V, int(rows_per_scale))."""
+    _chk(scale, f32, 'scale')
+    assert all(t.dtype == f32 and t.is_cuda and t.stride(1) == 1 for t in (logits_c, logits_u))
+    R, V = logits_c.shape
+    if tuple(logits_u.shape) != (R, V) or logits_u.stride(0) != logits_c.stride(0):
+        if name == 'logits_truncate':  # (its `rows` check has taken the shape, and it calls the conditional operand `logits`)
+            raise ValueError(f'{name}: logits_u (row stride {logits_u.stride(0)}) must have the row stride of logits ({logits_c.stride(0)})')
+        raise ValueError(f'{name}: logits_u {tuple(logits_u.shape)} (row stride {logits_u.stride(0)}) must have the shape and '
+                         f'the row stride of logits_c {(R, V)} ({logits_c.stride(0)})')
+    rows_per_scale = int(rows_per_scale)
+    if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
+        raise ValueError(f'{name}: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
+    return R, V, rows_per_scale
+
+
 def sample_race_guided(logits_c, logits_u, scale, rows_per_scale, E, noise_u=None, temperature=0.0, logit_div=1.0):
     """sample_race on lc + w * (lc - lu) (three rounded fp32 operations, lc == -inf stays -inf), w = scale[r // rows_per_scale]: logits_c,
     logits_u [R, V] f32 with one row stride, scale f32 [R // rows_per_scale] on the device -> (tok int64 [R], y f32 [R])."""
-    _chk(E, f32, 'E'), _chk(scale, f32, 'scale')
-    assert logits_c.dtype == f32 and logits_c.is_cuda and logits_c.stride(1) == 1
-    assert logits_u.dtype == f32 and logits_u.is_cuda and logits_u.stride(1) == 1
-    R, V = logits_c.shape
-    if tuple(logits_u.shape) != (R, V) or logits_u.stride(0) != logits_c.stride(0):
-        raise ValueError(f'sample_race_guided: logits_u {tuple(logits_u.shape)} (row stride {logits_u.stride(0)}) must have the shape and '
-                         f'the row stride of logits_c {(R, V)} ({logits_c.stride(0)})')
+    _chk(E, f32, 'E')
+    R, V, rows_per_scale = _guided_operands('sample_race_guided', logits_c, logits_u, scale, rows_per_scale)
     assert E.shape == (R, V) and E.is_contiguous()
-    rows_per_scale = int(rows_per_scale)
-    if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
-        raise ValueError(f'sample_race_guided: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
-    tok = torch.empty(R, device=logits_c.device, dtype=i64)
-    y = torch.empty(R, device=logits_c.device, dtype=f32)
+    tok, y = torch.empty(R, device=logits_c.device, dtype=i64), torch.empty(R, device=logits_c.device, dtype=f32)
     if noise_u is not None:
         _chk(noise_u, f32, 'noise_u')
     call('mmvid_sample_race_guided', _p(logits_c), _p(logits_u), logits_c.stride(0), _p(scale), rows_per_scale, _p(E), _p(noise_u),
@@ -658,17 +665,9 @@ def sample_race_guided_at(logits_c, logits_u, scale, rows_per_scale, E, logit_di
     """The token-only draw of sample_race (want_y False, no noise; R <= 1024) on the guided value of sample_race_guided: logits_c, logits_u
     [R, V] f32 with one row stride, scale f32 [R // rows_per_scale] on the device, E [R, V], or [draws, R, V] with step_dev (int32 device
     scalar: draw number step_dev - step0 is used) -> tok int64 [R] (tok_out if given)."""
-    _chk(E, f32, 'E'), _chk(scale, f32, 'scale')
-    assert logits_c.dtype == f32 and logits_c.is_cuda and logits_c.stride(1) == 1
-    assert logits_u.dtype == f32 and logits_u.is_cuda and logits_u.stride(1) == 1
-    R, V = logits_c.shape
-    if tuple(logits_u.shape) != (R, V) or logits_u.stride(0) != logits_c.stride(0):
-        raise ValueError(f'sample_race_guided_at: logits_u {tuple(logits_u.shape)} (row stride {logits_u.stride(0)}) must have the shape '
-                         f'and the row stride of logits_c {(R, V)} ({logits_c.stride(0)})')
+    _chk(E, f32, 'E')
+    R, V, rows_per_scale = _guided_operands('sample_race_guided_at', logits_c, logits_u, scale, rows_per_scale)
     assert E.shape[-2:] == (R, V) and E.is_contiguous() and (E.dim() == 2 or (E.dim() == 3 and step_dev is not None))
-    rows_per_scale = int(rows_per_scale)
-    if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
-        raise ValueError(f'sample_race_guided_at: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
     if tok_out is not None:
         _chk(tok_out, i64, 'tok_out')
         assert tok_out.shape == (R, )
@@ -699,13 +698,8 @@ def logits_truncate(logits, top_k=None, top_p=None, *, logits_u=None, scale=None
     if (logits_u is None) != (scale is None) or (logits_u is None) != (rows_per_scale is None):
         raise ValueError('logits_truncate: logits_u, scale and rows_per_scale come together (the guided form)')
     if logits_u is not None:
-        rows(logits_u, 'logits_u', (R, V)), _chk(scale, f32, 'scale')
-        if logits_u.stride(0) != logits.stride(0):
-            raise ValueError(f'logits_truncate: logits_u (row stride {logits_u.stride(0)}) must have the row stride of logits '
-                             f'({logits.stride(0)})')
-        rows_per_scale = int(rows_per_scale)
-        if rows_per_scale <= 0 or R % rows_per_scale or scale.numel() != R // rows_per_scale:
-            raise ValueError(f'logits_truncate: {scale.numel()} scales for R = {R} rows in groups of {rows_per_scale}')
+        rows(logits_u, 'logits_u', (R, V))
+        rows_per_scale = _guided_operands('logits_truncate', logits, logits_u, scale, rows_per_scale)[2]
     if out is None:
         out = torch.empty(R, V, device=logits.device, dtype=f32)
     else:

@@ -13,13 +13,15 @@ schedule and of the model -- independent of how many videos share the call.
 a keep-count schedule PER ROW, where `preserve` has one pattern and one count for the whole call.
 
 Classifier-free guidance (`uncond_emb`, `guidance_scale`): every step runs the tower a second time on the same tokens under the
-unconditional control, and the token race reads `lc + w * (lc - lu)` from the two logit tensors in one kernel
-(ops.sample_race_guided).  Scores, candidate choice, the dynamic stop and the given tokens belong to the conditional branch alone.
+unconditional control, and the token race reads `lc + w * (lc - lu)` from the two logit tensors.  Scores, candidate choice, the
+dynamic stop and the given tokens belong to the conditional branch alone.  The launches of a token draw (plain, truncated, guided, both)
+are token_draw.draw's; the argument rules of both samplers' keywords stand here, with the rule for the unconditional prompt of a guided call.
 """
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, token_draw
+from .artv_sampling import k_keep
 
 
 def schedule(mp_config, N):
@@ -181,6 +183,59 @@ def check_truncation(top_k, top_p, Tmax, V):
     return per_step(top_k, 'top_k', one_k), per_step(top_p, 'top_p', one_p)
 
 
+def check_truncation_artv(top_k, top_p, V):
+    """ART-V's scalar `top_k` / `top_p` (check_truncation at one step) -> (k | None, p | None), or None when neither can remove a class of V."""
+    trunc = check_truncation(top_k, top_p, 1, V)
+    k, p = (None, None) if trunc is None else (trunc[0][0], trunc[1][0])
+    return (k, p) if (k is not None and k < V) or (p is not None and p < 1.0) else None
+
+
+def check_guidance_artv(num_visuals, text_seq_len, total_tokens, num_image_tokens, B, guidance_scale, guidance_drop, negative_text, filter_thres):
+    """The ART-V sampler's guidance keywords (check_guidance and the rules of the token loop, before any device work) -> (drop, scale),
+    or None for the unguided call.  scale: a float, or a tensor [B] with one scale per video."""
+    drop = check_guidance(num_visuals, False, guidance_scale, guidance_drop, negative_text)
+    if drop is None:
+        return None
+    if isinstance(guidance_scale, (list, tuple, np.ndarray)) or (torch.is_tensor(guidance_scale) and guidance_scale.dim() > 1):
+        raise ValueError('guidance_scale: a per-token schedule (a sequence, or a tensor [steps, B]) is not accepted: the captured token '
+                         f'step reads one scale per video; pass a float or a tensor [B] = [{B}]')
+    if torch.is_tensor(guidance_scale):
+        if guidance_scale.dim() == 1 and guidance_scale.shape[0] != B:
+            raise ValueError(f'guidance_scale: a tensor must be [B] = [{B}] (one scale per video), got {tuple(guidance_scale.shape)}')
+        scale = guidance_scale.detach().to(torch.float32).expand(B)
+        finite = scale.is_cuda or bool(torch.isfinite(scale).all())  # (a tensor already on the device is not read back)
+    else:
+        try:
+            scale = float(guidance_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f'guidance_scale: expected a float or a tensor [{B}], got {type(guidance_scale).__name__}') from None
+        finite = np.isfinite(scale)
+    if not finite:
+        raise ValueError('guidance_scale: every scale must be finite')
+    if negative_text is not None and (not torch.is_tensor(negative_text) or negative_text.dim() != 2 or
+                                      tuple(negative_text[:, :text_seq_len].shape) != (B, text_seq_len)):
+        got = tuple(negative_text.shape) if torch.is_tensor(negative_text) else type(negative_text).__name__
+        raise ValueError(f'negative_text: expected int64 [B, text_seq_len] = [{B}, {text_seq_len}], got {got}')
+    if k_keep(filter_thres, total_tokens) < num_image_tokens:
+        raise ValueError(f'guidance_scale with filter_thres = {filter_thres}, which removes image classes: the torch.topk filter has no '
+                         'guided form; leave filter_thres where it keeps the block and truncate with top_k (or top_p)')
+    return drop, scale
+
+
+def scale_vector(scale, B, device):
+    """A float or a tensor -> fp32 [B] on the device: what the guided kernels read."""
+    if torch.is_tensor(scale):
+        return scale.to(device=device, dtype=torch.float32).expand(B).contiguous()
+    return torch.full((B, ), float(scale), dtype=torch.float32, device=device)
+
+
+def unconditional_inputs(text, visual, drop, negative_text):
+    """The unconditional prompt of a guided call -> (text_u, visual_u).  The text is `negative_text` when given, all pad when `drop`
+    names 'text', else `text`; the visual control (frames or tokens) is None when `drop` names 'visual', else `visual`."""
+    text_u = negative_text.to(text.device) if negative_text is not None else (torch.zeros_like(text) if 'text' in drop else text)
+    return text_u, None if 'visual' in drop else visual
+
+
 @torch.no_grad()
 def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1, mp_config=None,
                  long_mode='long', race=None, trace=None, given=None, given_unknown=None, uncond_emb=None, guidance_scale=None,
@@ -250,29 +305,19 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
 
     truncated = {}  # what the truncated draw of the current step read: {'logits_t', 'kept'} (the trace keeps it)
 
-    def draw_tokens(logits, logits_u, t, nb, Et, noise_u):
+    def draw_tokens(logits, logits_u, t, nb):  # step t, nb candidates per video -> (tokens, Y, the race variates)
         truncated.clear()
-        if trunc_on[t]:
-            guide = dict(logits_u=logits_u, scale=scale[t], rows_per_scale=nb * TS) if guided else {}
-            lg = ops.logits_truncate(logits, trunc[0][t], trunc[1][t], want_kept=trace is not None, **guide)
-            if trace is not None:
-                truncated.update(logits_t=lg[0], kept=lg[1])
-                lg = lg[0]
-            return ops.sample_race(lg, Et, noise_u, temp[t])
-        if not guided:
-            return ops.sample_race(logits, Et, noise_u, temp[t])
-        return ops.sample_race_guided(logits, logits_u, scale[t], nb * TS, Et, noise_u, temp[t])
-
-    def noise(name, t, shape):
-        if temp[t] == 0.0:
-            return None
-        return (race(name + '_noise_u', shape) if race is not None else torch.rand(shape, device=dev))
+        shape = (b * nb * TS, V)
+        Et = draw(f'tok{t}', shape)
+        noise_u = None if temp[t] == 0.0 else (race(f'tok{t}_noise_u', shape) if race is not None else torch.rand(shape, device=dev))
+        return (*token_draw.draw(logits, Et, logits_u=logits_u, scale=scale[t] if guided else None, rows_per_scale=nb * TS, noise_u=noise_u,
+                                 temperature=temp[t], trunc=(trunc[0][t], trunc[1][t]) if trunc_on[t] else None, want_y=True,
+                                 record=truncated if trace is not None else None), Et)
 
     # ---- step 0: everything that is not given is [MASK]
     out, logits = tower_logits(fixed_tok, None, 1)
     logits_u = tower_logits(fixed_tok, None, 1, uncond_emb)[1] if guided else None
-    E0 = draw('tok0', (b * TS, V))
-    I_new, Y = draw_tokens(logits, logits_u, 0, 1, E0, noise('tok0', 0, (b * TS, V)))
+    I_new, Y, E0 = draw_tokens(logits, logits_u, 0, 1)
     Y = Y.view(b, TS)
     I_tok = I_new.view(b, TS)
     if fixed is not None:
@@ -297,8 +342,7 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
         mask1 = ops.mp_select_keep(Y, Ek, fixed, keep_count(t))
         out, logits = tower_logits(I_tok, mask1, Bm)
         logits_u = tower_logits(I_tok, mask1, Bm, uncond_emb)[1] if guided else None
-        Et = draw(f'tok{t}', (b * Bm * TS, V))
-        Inew, Ynew = draw_tokens(logits, logits_u, t, Bm, Et, noise(f'tok{t}', t, (b * Bm * TS, V)))
+        Inew, Ynew, Et = draw_tokens(logits, logits_u, t, Bm)
         out2d = out.view(b * Bm * L, E)
         z_rel = ops.head_rows_fwd(out2d, rel_rows, rel_head[0].weight, rel_head[0].bias, rel_head[1].weight.view(-1),
                                   rel_head[1].bias, rel_head[0].eps)[0]

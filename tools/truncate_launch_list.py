@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The calls of both samplers on the tiny models of the tests, for a kernel-trace run: the kernel list of this tree must be the parent
-commit's (no launch added, none changed).  BERT and ART-V without the truncation keywords, and ART-V on every path of its token loop
-(mmvid_amd/artv_sampling.py): batch 4 captured, batch 4 with a `filter_thres` that filters (eager), batch 4 with top_k = 8 (captured with
-the truncation launch) and batch 2 (one launch per token).  Every ART-V call runs under a fixed seed and prints a digest of the token
-tensor it sampled: the two trees' outputs must be equal line for line.
+commit's (no launch added, none changed).  Every form of the token draw (mmvid_amd/token_draw.py) in both samplers: BERT plain, guided,
+with top_k = 8 and guided with top_p = 0.9; ART-V on every path of its token loop (mmvid_amd/artv_sampling.py): batch 4 captured, batch 4
+with a `filter_thres` that filters (eager), batch 4 with top_k = 8 (captured with the truncation launch), batch 4 guided, batch 4 guided
+with top_k = 8, and batch 2 (one launch per token).  Every call runs under a fixed seed and prints a digest of the tokens it sampled
+(BERT: img_seq): the two trees' outputs must be equal line for line.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python tools/truncate_launch_list.py [--root OTHER_CHECKOUT]
 
@@ -70,12 +71,22 @@ def artv_call(what, B, **kw):
     print(f'artv {what}: tokens {tuple(tokens.shape)} sha256 {hashlib.sha256(tokens.numpy().tobytes()).hexdigest()[:16]}')
 
 
+def bert_call(what, **kw):
+    torch.manual_seed(7)
+    img_seq = bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False, **kw)[2].cpu()
+    print(f'bert {what}: img_seq {tuple(img_seq.shape)} sha256 {hashlib.sha256(img_seq.numpy().tobytes()).hexdigest()[:16]}')
+
+
 for _ in range(2):
-    bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False)
-    bert.generate_images(text, mask_predict_steps=0, mp_config=mp, dynamic=False, guidance_scale=2.0, guidance_drop=('text', ))
+    bert_call('plain')
+    bert_call('guided', guidance_scale=2.0, guidance_drop=('text', ))
+    bert_call('top_k 8', top_k=8)  # [truncate -> plain race] at every step
+    bert_call('guided, top_p 0.9', guidance_scale=2.0, guidance_drop=('text', ), top_p=0.9)  # the guided truncation, then the plain race
     artv_call('batch 4', 4)  # the captured five-launch step
     artv_call('batch 4, filter_thres 0.999', 4, filter_thres=0.999)  # a filter_thres that filters: the eager torch.topk path
     artv_call('batch 4, top_k 8', 4, top_k=8)  # [head -> truncate -> draw -> embed -> tower] captured
+    artv_call('batch 4, guided', 4, guidance_scale=2.0)  # 8 tower rows, the guided token-only race, captured
+    artv_call('batch 4, guided, top_k 8', 4, guidance_scale=2.0, top_k=8)  # the guided truncation into its own buffer, then the plain race
     artv_call('batch 2', 2)  # one persistent launch per token
 torch.cuda.synchronize()
 print('done')
