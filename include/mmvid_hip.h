@@ -621,13 +621,13 @@ int mmvid_groupnorm_swish_nhwc_f16out(const float* x, int N, int64_t hw, int C, 
  * into `arena` (-1 = unused); w/b/ext_* are device pointers. */
 enum {
     MMVID_VQOP_IMG2NHWC8 = 0, /* ext_in img [N,3,H,W] f32 -> out_bf16 [N,H,W,8]                                  */
-    MMVID_VQOP_CONV = 1,      /* in0 x [N,H,W,C] bf16, w, b, Cout, mode; in1 residual (flags&1: f32); flags&2 clamp01;
-                                 flags&4: write GroupNorm partial sums of the output into `scratch` (a GN stats area);
-                                 flags&8: the strip kernel (mmvid_conv3x3_strip_nhwc; partial sums per 64 pixels);
-                                 flags&32: split-K by 4 through the fp32 workspace at `scratch` (mmvid_conv2d_nhwc_splitk)   */
-    MMVID_VQOP_GROUPNORM = 2, /* in0 [N,H,W,C] (flags&1: f32), w, b, eps, mode = swish, scratch = stats;
-                                 flags&2: the partial sums in `scratch` were written by the producing CONV (flags&8: per
-                                 64-pixel block instead of per 128)                                                  */
+    MMVID_VQOP_CONV = 1,      /* in0 x [N,H,W,C] bf16, w, b, Cout, mode; in1 residual (RES_F32: f32); CLAMP01;
+                                 EMIT_STATS: write GroupNorm partial sums of the output into `scratch` (a GN stats area);
+                                 STRIP: the strip kernel (mmvid_conv3x3_strip_nhwc; partial sums per 64 pixels);
+                                 SPLITK: split-K by 4 through the fp32 workspace at `scratch` (mmvid_conv2d_nhwc_splitk)     */
+    MMVID_VQOP_GROUPNORM = 2, /* in0 [N,H,W,C] (IN_F32: f32), w, b, eps, mode = swish, scratch = stats;
+                                 STATS_GIVEN: the partial sums in `scratch` were written by the producing CONV (BLOCKS64:
+                                 per 64-pixel block instead of per 128)                                              */
     MMVID_VQOP_CAST = 3,      /* in0 f32 -> out_bf16, N*H*W*C elements                                           */
     MMVID_VQOP_SPATIAL_ATTN = 4, /* in0,in1,in2 = q,k,v [N,H*W,C] bf16, eps = scale, scratch                        */
     MMVID_VQOP_VQ_ARGMIN = 5, /* in0 z [N*H*W, C] f32, w = codebook [Cout, C], b = ee -> ext_out int64            */
@@ -635,18 +635,35 @@ enum {
     MMVID_VQOP_NHWC2NCHW = 7, /* in0 [N,H,W,C] f32 -> ext_out [N,Cout,H,W] f32                                    */
     MMVID_VQOP_EXT_CAST = 8   /* ext_in f32 [N*H*W*C] -> out_bf16 (or out_f32 copy when strict): decode_train's z     */
 };
-/* flags & 16 (IMG2NHWC8, CONV, GROUPNORM, SPATIAL_ATTN, GATHER, EXT_CAST): the strict fp32 operator; every arena
+/* The bits of mmvid_vqgan_op_t.flags.  STRICT and SPLIT say which operator a record belongs to (neither: the bf16 operator); bits
+ * 1, 2 and 8 mean one thing on a CONV and another on a GROUPNORM, and have one name per meaning. */
+#define MMVID_VQFLAG_RES_F32 1     /* CONV: the residual at in1 is fp32 (else bf16)                                          */
+#define MMVID_VQFLAG_IN_F32 1      /* GROUPNORM: the input at in0 is fp32 (else bf16)                                        */
+#define MMVID_VQFLAG_CLAMP01 2     /* CONV: the epilogue (clamp(x,-1,1)+1)/2                                                 */
+#define MMVID_VQFLAG_STATS_GIVEN 2 /* GROUPNORM: the producing CONV (EMIT_STATS) wrote the partial sums in `scratch`         */
+#define MMVID_VQFLAG_EMIT_STATS 4  /* CONV: write the GroupNorm partial sums of the output into the stats area at `scratch`  */
+#define MMVID_VQFLAG_STRIP 8       /* CONV: the strip kernel (3x3, mode 0; its partial sums are per 64 pixels)               */
+#define MMVID_VQFLAG_BLOCKS64 8    /* GROUPNORM (with STATS_GIVEN): partial sums per 64 pixels instead of per 128            */
+/* STRICT (IMG2NHWC8, CONV, GROUPNORM, SPATIAL_ATTN, GATHER, EXT_CAST): the strict fp32 operator; every arena
  * tensor of such a plan is fp32 (out_f32 / in* are fp32), w is fp32 [Cout][taps][Cin]. */
 #define MMVID_VQFLAG_STRICT 16
-/* flags & 64 (IMG2NHWC8, CONV, GROUPNORM, CAST): the split operator.  IMG2NHWC8 / GROUPNORM / CAST write bf16 pair planes at
- * out_bf16 (in0 fp32); CONV reads pair planes at in0, w = w3, residual in1 fp32, writes out_f32 (flags&2 clamp01, flags&8 strip
- * form, flags&32 split-K by 4 through `scratch`, flags&4 GroupNorm partial sums of the output into the stats area `scratch`);
- * GROUPNORM flags&2 / flags&8 as for the bf16 operator (partial sums written by the producing CONV). */
+#define MMVID_VQFLAG_SPLITK 32     /* CONV: split-K by 4 through the fp32 workspace at `scratch`, fixed-order reduce         */
+/* SPLIT (IMG2NHWC8, CONV, GROUPNORM, CAST): the split (bf16-pair) operator.  IMG2NHWC8 / GROUPNORM / CAST write bf16 pair planes at
+ * out_bf16 (in0 fp32); CONV reads pair planes at in0, w = w3, residual in1 fp32, writes out_f32 (CLAMP01, STRIP, SPLITK and
+ * EMIT_STATS as for the bf16 operator); GROUPNORM STATS_GIVEN / BLOCKS64 as for the bf16 operator. */
 #define MMVID_VQFLAG_SPLIT 64
-/* flags & 128, together with SPLIT: GROUPNORM writes ONE fp16 plane at out_bf16 (mmvid_groupnorm_swish_nhwc_f16out); CONV (strip form,
- * flags&8) reads such a plane at in0 with w = fp16 [Cout][9][Cin] (mmvid_conv3x3_strip_nhwc_f16).  A split CONV in strip form with
+/* F16, together with SPLIT: GROUPNORM writes ONE fp16 plane at out_bf16 (mmvid_groupnorm_swish_nhwc_f16out); CONV (with STRIP)
+ * reads such a plane at in0 with w = fp16 [Cout][9][Cin] (mmvid_conv3x3_strip_nhwc_f16).  A split CONV with STRIP and
  * out_bf16 >= 0 also / only (out_f32 < 0) writes its result as pair planes there. */
 #define MMVID_VQFLAG_F16 128
+/* What mmvid_vqgan_check accepts.  The operator of a record: strict if STRICT, pair if SPLIT, else bf16; STRICT with SPLIT is refused.
+ *   operator | ops it has                                                | flags on a CONV, besides its own              | on a GROUPNORM
+ *   bf16     | all nine                                                  | RES_F32 CLAMP01 EMIT_STATS STRIP SPLITK       | IN_F32 STATS_GIVEN BLOCKS64
+ *   pair     | IMG2NHWC8 CONV GROUPNORM CAST                             | CLAMP01 EMIT_STATS STRIP SPLITK F16           | STATS_GIVEN BLOCKS64 F16
+ *   strict   | IMG2NHWC8 CONV GROUPNORM SPATIAL_ATTN GATHER EXT_CAST     | CLAMP01                                       | none
+ * Every other op takes no flag besides its operator's.  CONV: EMIT_STATS and SPLITK exclude each other (both use `scratch`) and need
+ * scratch >= 0; STRIP excludes CLAMP01 and SPLITK and needs mode 0; F16 needs STRIP; RES_F32 needs in1 >= 0; one of out_bf16 /
+ * out_f32 is given.  GROUPNORM: BLOCKS64 needs STATS_GIVEN; scratch >= 0. */
 typedef struct {
     int32_t op, mode;
     int32_t N, H, W, C;
@@ -660,6 +677,10 @@ typedef struct {
     float eps;
     int32_t pad;
 } mmvid_vqgan_op_t;
+/* Host only, no HIP call: MMVID_OK, or MMVID_ERR_ARG with the index of the first record the table above refuses, its op code and
+ * the offending flag by name in mmvid_last_error(). */
+int mmvid_vqgan_check(const mmvid_vqgan_op_t* ops, int nops);
+/* Checks the list first: a refused list enqueues nothing. */
 int mmvid_vqgan_run(const mmvid_vqgan_op_t* ops, int nops, void* arena, void* stream);
 
 /* hardware probe (tools/gpu_probe.py): which = 0 -> ds_read_b64_tr_b16 lane layout | 1 -> LDS-DMA through a buffer descriptor |

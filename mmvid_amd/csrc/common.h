@@ -105,6 +105,9 @@ __device__ __forceinline__ void mfma_settle(f32x16& acc) { asm volatile("s_nop 1
 __device__ __forceinline__ void mfma_settle(f32x4& acc) { asm volatile("s_nop 15" : "+v"(acc)); }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// A GroupNorm statistics area, fp32 [N*(2*C + 64*ceil(hw/64))]: the per-channel pairs [N][C][2] first, then the per-block partial sums
+// [N][blocks][32][2], which start here (the one statement of that offset; ops.py's _gn_stats_partials is its Python twin)
+static inline float* gn_stats_partials(float* area, int N, int C) { return area + (long)N * C * 2; }
 // Run-time options: set by environment variable at first use or through mmvid_set_option().
 //   graphs   MMVID_GRAPHS   1 = library-level hipGraph replay of the long launch sequences (tower passes, VQGAN plans); default 0 -- the
 //                           training engine captures the whole step instead (mmvid_amd/engine.py)

@@ -826,8 +826,8 @@ extern "C" int mmvid_groupnorm_swish_nhwc(const void* x, int x_is_bf16, int N, i
     hipStream_t s = (hipStream_t)stream;
     const int pix_per_block = 256;
     int nblk = partial_blocks;
-    float* ab = stats_scratch;                         // [N][C][2]
-    float* partial = stats_scratch + (long)N * C * 2;  // [N][nblk][32][2]
+    float* ab = stats_scratch;                                  // [N][C][2]
+    float* partial = gn_stats_partials(stats_scratch, N, C);  // [N][nblk][32][2]
     const long chunks = (long)N * hw * (C / 8);
     if (partial_blocks == 0 && hw <= pix_per_block && (C & (C - 1)) == 0) {  // one launch does all three steps (whole groups per 64-channel block)
         if (x_is_bf16)
@@ -886,8 +886,8 @@ static int groupnorm_split_launch(const float* x, int N, int64_t hw, int C, cons
     hipStream_t s = (hipStream_t)stream;
     const int pix_per_block = 256;
     int nblk = partial_blocks;  // > 0: the producing convolution's epilogue already wrote that many partial blocks per image
-    float* mr = stats_scratch;                         // [N][C][2]
-    float* partial = stats_scratch + (long)N * C * 2;  // [N][nblk][32][2]
+    float* mr = stats_scratch;                                  // [N][C][2]
+    float* partial = gn_stats_partials(stats_scratch, N, C);  // [N][nblk][32][2]
     if (partial_blocks == 0) {
         nblk = cdiv(hw, pix_per_block);
         hipLaunchKernelGGL(groupnorm_stats_kernel<float>, dim3(nblk, N), dim3(256), 0, s, x, (long)hw, C, pix_per_block, partial);

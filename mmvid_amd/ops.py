@@ -298,10 +298,21 @@ def layernorm_bwd_reduce_multi(items, blocks, E):
     call('mmvid_layernorm_bwd_reduce_multi', len(items), arr, blocks, E, _stream())
 
 
+def gn_stats_floats(N, hw, C):
+    """Size of a GroupNorm statistics area: [N][C][2] per-channel pairs, then partial sums [N][blocks][32][2] (blocks of 128 pixels,
+    or of 64 for the strip convolution: sized for the finer one).  The one statement of the layout on the Python side, with
+    _gn_stats_partials; csrc/common.h has the C side."""
+    return N * (2 * C + 64 * ((hw + 63) // 64))
+
+
+def _gn_stats_partials(stats, N, C):
+    """Pointer to the partial sums of a statistics area for N images of C channels (None without an area)."""
+    return ctypes.c_void_p(stats.data_ptr() + N * C * 2 * 4) if stats is not None else None
+
+
 def gn_stats_buffer(N, hw, C, device):
-    """fp32 scratch of mmvid_groupnorm_swish_nhwc: [N][C][2] affine, then partial sums [N][blocks][32][2] (blocks of 128
-    pixels, or of 64 for the strip convolution: sized for the finer one)."""
-    return torch.empty(N * (2 * C + 64 * ((hw + 63) // 64)), device=device, dtype=f32)
+    """fp32 scratch of mmvid_groupnorm_swish_nhwc (gn_stats_floats)."""
+    return torch.empty(gn_stats_floats(N, hw, C), device=device, dtype=f32)
 
 
 def conv3x3_strip(x, w, bias, residual=None, out_dtype=bf16, also_bf16=False, gn_stats=None):
@@ -314,9 +325,8 @@ def conv3x3_strip(x, w, bias, residual=None, out_dtype=bf16, also_bf16=False, gn
     o16 = torch.empty(N, H, W, Cout, device=x.device, dtype=bf16) if (also_bf16 and out_dtype == f32) else None
     rb = residual if (residual is not None and residual.dtype == bf16) else None
     rf = residual if (residual is not None and residual.dtype == f32) else None
-    gp = ctypes.c_void_p(gn_stats.data_ptr() + N * Cout * 2 * 4) if gn_stats is not None else None
     call('mmvid_conv3x3_strip_nhwc', _p(x), N, H, W, Cin, _p(w), _p(bias), Cout, _p(rb), _p(rf),
-         _p(out) if out_dtype == bf16 else _p(o16), _p(out) if out_dtype == f32 else None, gp, _stream())
+         _p(out) if out_dtype == bf16 else _p(o16), _p(out) if out_dtype == f32 else None, _gn_stats_partials(gn_stats, N, Cout), _stream())
     return (out, o16) if o16 is not None else out
 
 
@@ -502,12 +512,10 @@ def conv2d_nhwc(x, w, bias, mode, residual=None, clamp01=False, out_dtype=bf16, 
     out = torch.empty(N, Ho, Wo, Cout, device=x.device, dtype=out_dtype)
     rb = residual if (residual is not None and residual.dtype == bf16) else None
     rf = residual if (residual is not None and residual.dtype == f32) else None
-    gp = None
-    if gn_stats is not None:
-        gp = ctypes.c_void_p(gn_stats.data_ptr() + N * Cout * 2 * 4)
     ws = torch.empty(splitk * N * Ho * Wo * Cout, device=x.device, dtype=f32) if splitk > 1 else None
     call('mmvid_conv2d_nhwc_splitk', mode, _p(x), N, H, W, Cin, _p(w), _p(bias), Cout, _p(rb), _p(rf), int(clamp01),
-         _p(out) if out_dtype == bf16 else None, _p(out) if out_dtype == f32 else None, gp, int(splitk), _p(ws), _stream())
+         _p(out) if out_dtype == bf16 else None, _p(out) if out_dtype == f32 else None, _gn_stats_partials(gn_stats, N, Cout), int(splitk), _p(ws),
+         _stream())
     return out
 
 
@@ -551,7 +559,7 @@ def groupnorm_swish_split(x, w, b, eps=1e-6, swish=True):
     _chk(x, f32, 'x')
     N, H, W, C = x.shape
     out = torch.empty(2, N, H, W, C, device=x.device, dtype=bf16)
-    st = torch.empty(N * (2 * C + 64 * ((H * W + 63) // 64)), device=x.device, dtype=f32)
+    st = gn_stats_buffer(N, H * W, C, x.device)
     call('mmvid_groupnorm_swish_nhwc_split', _p(x), N, H * W, C, _p(w), _p(b), float(eps), int(swish), _p(st), 0, _p(out), _stream())
     return out
 
@@ -561,7 +569,7 @@ def groupnorm_swish_f16(x, w, b, eps=1e-6, swish=True):
     _chk(x, f32, 'x')
     N, H, W, C = x.shape
     out = torch.empty(N, H, W, C, device=x.device, dtype=torch.float16)
-    st = torch.empty(N * (2 * C + 64 * ((H * W + 63) // 64)), device=x.device, dtype=f32)
+    st = gn_stats_buffer(N, H * W, C, x.device)
     call('mmvid_groupnorm_swish_nhwc_f16out', _p(x), N, H * W, C, _p(w), _p(b), float(eps), int(swish), _p(st), 0, _p(out), _stream())
     return out
 

@@ -19,15 +19,13 @@ from . import _lib, ops
 
 bf16, f32 = torch.bfloat16, torch.float32
 
-# mmvid_vqgan_op_t.flags (include/mmvid_hip.h); bits 1, 2 and 8 mean one thing on a CONV and another on a GROUPNORM
-RES_F32 = IN_F32 = 1         # CONV: the residual at in1 is fp32 | GROUPNORM: the input is fp32
-CLAMP01 = STATS_GIVEN = 2    # CONV: (clamp(x,-1,1)+1)/2 epilogue | GROUPNORM: the producing CONV wrote the partial sums in `scratch`
-EMIT_STATS = 4               # CONV: write the GroupNorm partial sums of the output into the stats area at `scratch`
-STRIP = BLOCKS64 = 8         # CONV: the strip kernel (csrc/conv_strip.hip) | GROUPNORM: partial sums per 64 pixels instead of per 128
-STRICT = 16                  # MMVID_VQFLAG_STRICT: the fp32-accurate operator (csrc/strict.hip); all planned tensors are fp32
-SPLITK = 32                  # CONV: split-K by 4 through the fp32 workspace at `scratch`, fixed-order reduce
-SPLIT = 64                   # MMVID_VQFLAG_SPLIT: the bf16-pair operator; planned tensors are fp32 or pair planes [2][n,h,w,c] bf16
-F16 = 128                    # MMVID_VQFLAG_F16 (with SPLIT): a GroupNorm that writes one fp16 plane / the strip convolution that reads it
+# The flags and op codes of mmvid_vqgan_op_t come from include/mmvid_hip.h, which says what each means and which go together (bits
+# 1, 2 and 8 mean one thing on a CONV and another on a GROUPNORM).  A name the header lacks is a KeyError here, at import.
+FLAG_NAMES = ('RES_F32', 'IN_F32', 'CLAMP01', 'STATS_GIVEN', 'EMIT_STATS', 'STRIP', 'BLOCKS64', 'STRICT', 'SPLITK', 'SPLIT', 'F16')
+RES_F32, IN_F32, CLAMP01, STATS_GIVEN, EMIT_STATS, STRIP, BLOCKS64, STRICT, SPLITK, SPLIT, F16 = (
+    _lib.HEADER.constants['MMVID_VQFLAG_' + name] for name in FLAG_NAMES)
+OP_NAMES = {'OP_IMG': 'IMG2NHWC8', 'OP_CONV': 'CONV', 'OP_GN': 'GROUPNORM', 'OP_CAST': 'CAST', 'OP_ATTN': 'SPATIAL_ATTN',
+            'OP_VQ': 'VQ_ARGMIN', 'OP_GATHER': 'GATHER', 'OP_NCHW': 'NHWC2NCHW', 'OP_EXT': 'EXT_CAST'}  # the planner's name -> the header's
 
 
 def _pow2_at_least8(c):
@@ -84,7 +82,8 @@ class _Plan:
 
 class _Planner:
     """What the three operators share.  An operator implements image, conv, gn, cast, attn_block, gather and external_z."""
-    OP_IMG, OP_CONV, OP_GN, OP_CAST, OP_ATTN, OP_VQ, OP_GATHER, OP_NCHW, OP_EXT = range(9)
+    OP_IMG, OP_CONV, OP_GN, OP_CAST, OP_ATTN, OP_VQ, OP_GATHER, OP_NCHW, OP_EXT = (
+        _lib.HEADER.constants['MMVID_VQOP_' + name] for name in OP_NAMES.values())
     STRICT, SPLIT, F16 = STRICT, SPLIT, F16
     strict = split = False  # which operator this is, for readers of a planner; no method branches on them
 
@@ -145,9 +144,7 @@ class _Planner:
         return 0, -1, None
 
     def _gn_stats(self, n, hw, c):
-        # per image: the per-channel affine [C][2], then partial sums [blocks][32][2] for blocks of 64 pixels (the strip
-        # convolution's granularity; 128-pixel producers use the first half)
-        return self.alloc((n * (2 * c + 64 * ((hw + 63) // 64)), ), f32)
+        return self.alloc((ops.gn_stats_floats(n, hw, c), ), f32)
 
     def _gn_given_stats(self, x):
         """The stats area of a GroupNorm that reads x and its flags: partial sums already written by the producing convolution's

@@ -104,9 +104,11 @@ def test_real_header_every_function_and_struct_once(real):
     hdr = re.sub(r'/\*.*?\*/', ' ', open(HEADER_PATH).read(), flags=re.S)
     protos = re.findall(r'\b(mmvid_\w+)\s*\(', hdr)
     typedefs = re.findall(r'\}\s*(\w+)\s*;', re.sub(r'extern "C" \{|enum \{[^}]*\};', ' ', hdr))
-    assert len(protos) == len(set(protos)) == 143 and list(real.functions) == protos
+    assert len(protos) == len(set(protos)) == 144 and list(real.functions) == protos
     assert len(typedefs) == len(set(typedefs)) == 10 and list(real.structs) == typedefs
     assert real.constants['MMVID_ABI_VERSION'] == 3 and real.constants['MMVID_VQOP_EXT_CAST'] == 8
+    assert real.constants['MMVID_VQFLAG_STRIP'] == real.constants['MMVID_VQFLAG_BLOCKS64'] == 8  # two names of one bit are both kept
+    assert real.functions['mmvid_vqgan_check'] == (I, [POINTER(real.structs['mmvid_vqgan_op_t']), I])
     assert real.functions['mmvid_gemm_dw_multi_fill'] == (D, [I, POINTER(real.structs['mmvid_dw_kind_t']), I])
     assert real.functions['mmvid_set_option'] == (I, [c_char_p, I]) and real.functions['mmvid_last_error'] == (c_char_p, [])
     assert [ctypes.sizeof(s) for s in real.structs.values()] == [64, 32, 80, 192, 48, 136, 120, 96, 28, 144]

@@ -386,8 +386,8 @@ def test_vqgan_plan_structure_config2(monkeypatch):
     qkv = [o for o in ops_ if o.op == pl.OP_CONV and o.mode == 3 and o.Cout == 3 * o.C]
     assert len(qkv) == 3 and {o.out_bf16 for o in qkv} == {o.in0 for o in attn}
     assert kinds.count(pl.OP_GN) == 28 and kinds.count(pl.OP_ATTN) == 3 and kinds[-1] == pl.OP_VQ
-    fused_gn = [o for o in ops_ if o.op == pl.OP_GN and o.flags & 2]
-    emitting = [o for o in ops_ if o.op == pl.OP_CONV and o.flags & 4]
+    fused_gn = [o for o in ops_ if o.op == pl.OP_GN and o.flags & P.STATS_GIVEN]
+    emitting = [o for o in ops_ if o.op == pl.OP_CONV and o.flags & P.EMIT_STATS]
     # every level but 8x8 (64 pixels) fuses: 128^2, 64^2, 32^2, 16^2 have hw % 128 == 0 and >= 128 channels
     assert len(fused_gn) == sum(1 for o in ops_ if o.op == pl.OP_GN and (o.H * o.W) % 128 == 0 and o.C % 128 == 0)
     assert len(fused_gn) >= 18 and {o.scratch for o in fused_gn} <= {o.scratch for o in emitting}
@@ -401,7 +401,7 @@ def test_vqgan_plan_structure_config2(monkeypatch):
 
 
 def test_vqgan_plan_structure_split_mode(monkeypatch):
-    """vae.strict = 'split': every convolution is the pair operator (flag 64) on pair planes and writes fp32; GroupNorm and the
+    """vae.strict = 'split': every convolution is the pair operator (flag SPLIT) on pair planes and writes fp32; GroupNorm and the
     image layout write planes; attention is the fp32 operator; no bf16-operator op is left in the plan."""
     from mmvid_amd import vae as V, vqgan_plan as P
     v = V.VQGanVAE1024(None, 128)
@@ -416,11 +416,11 @@ def test_vqgan_plan_structure_split_mode(monkeypatch):
     # every convolution writes fp32, except the last one of levels 0-2 (strip form, read only by the level's Downsample convolution): it
     # stores the bf16 pair itself -- no fp32 store, no cast pass in front of the Downsample
     planes_only = [o for o in convs if o.out_f32 < 0]
-    assert len(planes_only) == 3 and all(o.out_bf16 >= 0 and o.flags & 8 and o.in1 >= 0 for o in planes_only)
+    assert len(planes_only) == 3 and all(o.out_bf16 >= 0 and o.flags & P.STRIP and o.in1 >= 0 for o in planes_only)
     assert all(o.out_bf16 < 0 for o in convs if o.out_f32 >= 0)
     assert sum(1 for o in ops_ if o.op == pl.OP_CAST) == 7     # fp32 -> pair planes in front of the remaining non-GroupNorm readers
-    assert sum(1 for o in convs if o.flags & 8) == 12          # the strip form at 32x32 and above
-    assert sum(1 for o in convs if o.flags & 32) >= 4          # split-K on the 8x8 layers
+    assert sum(1 for o in convs if o.flags & P.STRIP) == 12    # the strip form at 32x32 and above
+    assert sum(1 for o in convs if o.flags & P.SPLITK) >= 4    # split-K on the 8x8 layers
     assert all(o.flags & pl.SPLIT for o in ops_ if o.op in (pl.OP_GN, pl.OP_CAST, pl.OP_IMG))
     assert all(o.flags & pl.STRICT for o in ops_ if o.op == pl.OP_ATTN)
     w3, b, cout = v._cw(v.model.encoder.conv_in, 'pair')
@@ -432,7 +432,7 @@ def test_vqgan_plan_structure_split_mode(monkeypatch):
 
 
 def test_vqgan_plan_structure_mixed_mode(monkeypatch):
-    """vae.strict = 'mixed': the plan of 'split' with the F16 flag (128) on exactly the 3x3 residual-block convolutions of the 128x128,
+    """vae.strict = 'mixed': the plan of 'split' with the F16 flag on exactly the 3x3 residual-block convolutions of the 128x128,
     64x64 and 32x32 levels and on the GroupNorms that feed them -- 12 of the encoder's 45 convolutions, 82 % of its multiply-adds; the
     decoder's plan is the pair operator's."""
     from mmvid_amd import vae as V, vqgan_plan as P
@@ -443,7 +443,7 @@ def test_vqgan_plan_structure_mixed_mode(monkeypatch):
     P.plan_encode(pl, v.model, 4, 128)
     convs = [o for o in pl.ops if o.op == pl.OP_CONV]
     f16 = [o for o in convs if o.flags & pl.F16]
-    assert len(convs) == 45 and len(f16) == 12 and all(o.flags & pl.SPLIT and o.flags & 8 and o.H >= 32 and o.C in (128, 256) for o in f16)
+    assert len(convs) == 45 and len(f16) == 12 and all(o.flags & pl.SPLIT and o.flags & P.STRIP and o.H >= 32 and o.C in (128, 256) for o in f16)
     gns = [o for o in pl.ops if o.op == pl.OP_GN and o.flags & pl.F16]
     assert len(gns) == 12 and {o.out_bf16 for o in gns} == {o.in0 for o in f16}  # each reads the plane its GroupNorm wrote
 

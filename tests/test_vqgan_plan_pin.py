@@ -46,12 +46,19 @@ def _vae(size):
     return _model[size]
 
 
-def describe(strict, stream, kind, n, size_or_hw):
-    """One plan through vae._plan() -> (the fixture's record of it, the ops as printable rows)."""
+def planned(strict, stream, kind, n, size_or_hw):
+    """One plan through vae._plan(), on the CPU (tests/test_vqgan_oplist_host.py shows the same plans to mmvid_vqgan_check)."""
     v = _vae(size_or_hw if kind == 'enc' else 16 * size_or_hw)
     v.strict, v.stream = strict, stream
     v._prep.clear()  # (prepared weights and arenas of the case before: nothing of a plan depends on them)
     plan = v._plan(kind, n, size_or_hw)
+    v._prep.clear()
+    return plan
+
+
+def describe(strict, stream, kind, n, size_or_hw):
+    """One plan -> (the fixture's record of it, the ops as printable rows)."""
+    plan = planned(strict, stream, kind, n, size_or_hw)
     rank, rows = {}, []
     for o in plan.ops:
         w = rank.setdefault(o.w, len(rank)) if o.w else -1
@@ -59,7 +66,6 @@ def describe(strict, stream, kind, n, size_or_hw):
     rec = {'nops': len(plan.ops), 'arena': plan.arena.numel(), 'patches': [list(p) for p in plan.patches],
            'kept': {k: [off, list(shape)] for k, (off, shape) in plan.kept.items()},
            'ops': [hashlib.sha256(repr(r).encode()).hexdigest()[:8] for r in rows]}
-    v._prep.clear()
     return rec, rows
 
 

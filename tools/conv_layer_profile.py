@@ -10,7 +10,7 @@ from collections import OrderedDict
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from mmvid_amd import _lib, ops
+from mmvid_amd import _lib, ops, vqgan_plan as P
 from mmvid_amd.vae import VQGanVAE1024
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 96
@@ -47,18 +47,18 @@ for i in range(len(plan.ops)):
     if kind == 'conv':
         taps = 1 if o.mode == 3 else 9
         flops = 2.0 * N * Ho * Wo * o.Cout * taps * o.C
-        in_b = 4 if (o.flags & 64 and not o.flags & 128) else 2  # pair planes / one fp16 or bf16 plane
+        in_b = 4 if (o.flags & P.SPLIT and not o.flags & P.F16) else 2  # pair planes / one fp16 or bf16 plane
         byts = N * H * W * o.C * in_b + N * Ho * Wo * o.Cout * ((2 if o.out_bf16 >= 0 else 0) + (4 if o.out_f32 >= 0 else 0)) + \
-            (N * Ho * Wo * o.Cout * (4 if (o.flags & 1 or o.flags & 64) else 2) if o.in1 >= 0 else 0)
+            (N * Ho * Wo * o.Cout * (4 if (o.flags & P.RES_F32 or o.flags & P.SPLIT) else 2) if o.in1 >= 0 else 0)
         key = (kind, f'm{o.mode} {H}x{W} {o.C}->{o.Cout}' + (' +res' if o.in1 >= 0 else '') + (' f32out' if o.out_f32 >= 0 else '') +
-               (' +bf16' if o.out_f32 >= 0 and o.out_bf16 >= 0 else '') + (' +gnstats' if o.flags & 4 else '') + (' f16' if o.flags & 128 else (' pair' if o.flags & 64 else '')) +
-               (' splitk' if o.flags & 32 else ''))
+               (' +bf16' if o.out_f32 >= 0 and o.out_bf16 >= 0 else '') + (' +gnstats' if o.flags & P.EMIT_STATS else '') + (' f16' if o.flags & P.F16 else (' pair' if o.flags & P.SPLIT else '')) +
+               (' splitk' if o.flags & P.SPLITK else ''))
     elif kind == 'gn':
-        f32in = bool(o.flags & 1 or o.flags & 64)
-        outb = 4 if (o.flags & 64 and not o.flags & 128) else 2
+        f32in = bool(o.flags & P.IN_F32 or o.flags & P.SPLIT)
+        outb = 4 if (o.flags & P.SPLIT and not o.flags & P.F16) else 2
         byts = N * H * W * o.C * ((4 if f32in else 2) + outb)
-        key = (kind, f'{H}x{W} C{o.C} ' + ('f32in' if f32in else 'bf16in') + (' fused-stats' if o.flags & 2 else ' own-stats') +
-               (' ->f16' if o.flags & 128 else (' ->pair' if o.flags & 64 else '')))
+        key = (kind, f'{H}x{W} C{o.C} ' + ('f32in' if f32in else 'bf16in') + (' fused-stats' if o.flags & P.STATS_GIVEN else ' own-stats') +
+               (' ->f16' if o.flags & P.F16 else (' ->pair' if o.flags & P.SPLIT else '')))
     elif kind == 'cast':
         byts = N * H * W * o.C * 8
         key = (kind, f'{H}x{W} C{o.C}')
