@@ -10,7 +10,11 @@ Classifier-free guidance (`guide`: one fp32 scale per video, on the device): the
 rows 0..B-1 under the conditional prompt and rows B..2B-1 under the unconditional one.  One head launch gives both logit blocks, the
 draw races lc + w * (lc - lu), and the embedding launch writes the drawn token's row for both halves: the launches of a guided token
 are the unguided token's, and launch_loop captures them the same way.  A guided call never takes token_launch_loop.  Which launches
-make a draw (plain, truncated, guided, both) is token_draw.draw's decision; TokenLoop.draw hands it the static buffers."""
+make a draw (plain, truncated, guided, both) is token_draw.draw's decision; TokenLoop.draw hands it the static buffers.
+
+Video prediction (`given`: known frames per video, sample_given): a frame mask splits the target sequence into runs (segments).  A known
+run enters through the prefill, the prompt and every frame so far once more from position 0; an unknown run is a TokenLoop of its own
+length (`steps`) that starts at the run's first position, on a fresh decode session.  A generated token runs the launches above."""
 import os
 
 import torch
@@ -33,13 +37,16 @@ def keep_top(logits, k):
 class TokenLoop:
     """The buffers of one sampling call and the two halves of a token, draw(step) and advance()."""
 
-    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide=None, trace=None):
+    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide=None, trace=None, steps=None):
         rows, dev = h.shape[0], h.device  # the tower's rows: B, or 2B under guidance (h = [conditional; unconditional])
         B = rows // 2 if guide is not None else rows
         c0, c1 = model._allowed_range(model.control_seq_len)
         self.model, self.ln, self.first_pos, self.temperature, self.race, self.trunc = model, model.to_logits[0], first_pos, temperature, race, trunc
         self.guide, self.trace = guide, trace
-        self.V, self.steps, self.k_keep = c1 - c0, model.target_seq_len, k_keep(filter_thres, model.total_tokens)
+        # steps: the tokens of this loop, a run of unknown frames (None: the whole target sequence); tok0: the run's first token as an
+        # index in the target sequence, which names the injected variates
+        self.V, self.steps, self.k_keep = c1 - c0, model.target_seq_len if steps is None else int(steps), k_keep(filter_thres, model.total_tokens)
+        self.tok0 = first_pos - model.control_seq_len - 1
         self.w_blk, self.b_blk = model._w16()[c0:c1], model.to_logits[1].bias.detach()[c0:c1].contiguous()
         self.pos_rows, self.iemb = model._pos_rows().detach().contiguous(), model.image_emb.weight.detach()
         self.sess = model.transformer.decode_session(cache, first_pos, graph=False)
@@ -73,7 +80,7 @@ class TokenLoop:
         lg = keep_top(self.logits, self.k_keep) if self.guide is None else self.lc
         E, at = self.variates
         if self.race is not None:
-            E.copy_(self.race(f'tok{step}', tuple(E.shape)))
+            E.copy_(self.race(f'tok{self.tok0 + step}', tuple(E.shape)))
         elif self.E_all is None:
             E.exponential_()
         token_draw.draw(lg, E, trunc=self.trunc, logit_div=T, want_y=False, tok_out=self.tok, record=rec, **self.guided, **at,
@@ -164,11 +171,12 @@ def token_launch_loop(loop):
     return launch_loop(loop, good_step + 1)
 
 
-def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None, guide=None, trace=None):
-    """h [B, dim]: the hidden state of the prompt's last position, `cache` filled below first_pos -> the sampled tokens, target_seq_len columns [B, 1].
+def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None, guide=None, trace=None, steps=None):
+    """h [B, dim]: the hidden state of the prompt's last position, `cache` filled below first_pos -> the sampled tokens, target_seq_len columns [B, 1]
+    (`steps` columns for a run of that many tokens that starts at first_pos: sample_given).
     guide (fp32 [B] on the device): h and the cache hold 2B sequences, conditional then unconditional.  trace (a list): one dict of clones
     per token (logits, E, tok, x_in for every token but the last; scale when guided; logits_t and kept when truncated), eager loop."""
-    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide, trace)
+    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide, trace, steps)
     capture = race is None and trace is None and loop.k_keep >= loop.V and not model.stable and loop.steps > 4
     # (the one-launch token has no truncation and no second branch in it: a call with top_k / top_p or guidance takes the separate
     # launches; MMVID_DECODE_TOKEN=0: all do)
@@ -176,3 +184,113 @@ def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=No
             os.environ.get('MMVID_DECODE_TOKEN', '1') != '0'):
         return token_launch_loop(loop)
     return launch_loop(loop, 0, capture)
+
+
+# ---- video prediction: known frames enter through the prefill ---------------------------------------------------------------------------
+def segments(mask_row):
+    """The runs of a frame mask (T values, non-zero = known) -> [(known, frame0, frames)], in frame order.  Pure host code."""
+    row = [bool(v) for v in (mask_row.tolist() if torch.is_tensor(mask_row) else mask_row)]
+    runs = []
+    for t, k in enumerate(row):
+        if runs and runs[-1][0] == k:
+            runs[-1] = (k, runs[-1][1], runs[-1][2] + 1)
+        else:
+            runs.append((k, t, 1))
+    return runs
+
+
+def group_rows(mask):
+    """Rows of a [B, T] mask with the same pattern -> [(pattern as a tuple of 0 / 1, [rows])], in order of first appearance."""
+    groups = {}
+    for r, row in enumerate(mask.tolist() if torch.is_tensor(mask) else mask):
+        groups.setdefault(tuple(int(bool(v)) for v in row), []).append(r)
+    return list(groups.items())
+
+
+def scatter_rows(parts, B):
+    """[(rows, tokens [len(rows), L])] of disjoint row sets that cover 0 .. B-1 -> tokens [B, L] (one part over all rows: that tensor)."""
+    if len(parts) == 1 and list(parts[0][0]) == list(range(B)):
+        return parts[0][1]
+    first = parts[0][1]
+    out = torch.empty((B, ) + tuple(first.shape[1:]), dtype=first.dtype, device=first.device)
+    seen = 0
+    for rows, tok in parts:
+        out[torch.as_tensor(list(rows), dtype=torch.long, device=first.device)] = tok
+        seen += len(rows)
+    if seen != B:
+        raise ValueError(f'scatter_rows: {seen} rows for a batch of {B}')
+    return out
+
+
+def check_frame_mask(mask, B, T):
+    """A mask of known frames, [B, T] or [T], bool or uint8 -> uint8 [B, T] on the host, or ValueError."""
+    mask = torch.as_tensor(mask)
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'given: the mask must be bool or uint8, got {mask.dtype}')
+    if mask.dim() > 2:
+        raise ValueError(f'given: a token-grid or pixel mask {tuple(mask.shape)} cannot be honoured by a raster-order model (a token cannot '
+                         f'condition on later tokens of its frame): expected whole frames, [B, T] or [T] with T = {T}')
+    if tuple(mask.shape) not in ((T, ), (B, T)):
+        raise ValueError(f'given: the mask must be [B, T] = [{B}, {T}] or [T], got {tuple(mask.shape)}')
+    mask = (mask != 0).to(torch.uint8).cpu()
+    if mask.dim() == 1:
+        mask = mask.view(1, T).expand(B, T)
+    return mask.contiguous()
+
+
+def check_given(given, B, T, n, V):
+    """The `given` of DALLE.generate_images -> (mask [B, T] uint8 on the host, tokens int64 [B, T * n] where they were), or ValueError.
+    An ART-V model predicts tokens in raster order, frame after frame: it can condition on whole known frames that come BEFORE what it
+    generates and on nothing else, so a mask per token or per pixel is refused.  One host read when the tokens are on a device: the count
+    of known ids outside [0, V)."""
+    if not isinstance(given, (tuple, list)) or len(given) != 2:
+        raise ValueError('given: expected (mask, tokens)')
+    mask, tokens = given
+    mask = check_frame_mask(mask, B, T)
+    if not torch.is_tensor(tokens) or tokens.dtype != torch.int64 or tuple(tokens.shape) != (B, T * n):
+        got = f'{tokens.dtype} {tuple(tokens.shape)}' if torch.is_tensor(tokens) else type(tokens).__name__
+        raise ValueError(f'given: the tokens must be int64 [B, T * n] = [{B}, {T * n}], got {got}')
+    known = mask.bool().view(B, T, 1).expand(B, T, n).reshape(B, T * n).to(tokens.device)
+    outside = int((known & ((tokens < 0) | (tokens >= V))).sum())
+    if outside:
+        raise ValueError(f'given: {outside} known token ids are outside [0, num_image_tokens) = [0, {V})')
+    return mask, tokens
+
+
+def sample_given(model, prompt, pattern, known, filter_thres, temperature, race, trunc=None, guide=None, trace=None):
+    """One pass through the segments of a frame mask for rows that share it.  prompt [rows, 1 + control_seq_len]: <bos> text visual ids
+    (rows = B, or 2B under guidance); pattern: the T mask values; known int64 [B, T * n], read under the mask -> tokens [B, T * n].
+
+    A run of known frames draws nothing: its tokens join the prefix, and the whole prefix (prompt and every frame up to the end of the
+    run) goes through the tower's prefill from position 0 once more, which rewrites those cache rows -- the known frames get their keys
+    and values exactly as the prompt's tokens do -- and gives the hidden state of the last known position, from which the next token is
+    drawn.  A run of unknown frames is a TokenLoop of its own length over a fresh decode session, under the rules of `sample` (capture
+    above 4 tokens, the one-launch token at batch 1-2): a generated token runs the launches it runs in a call without known frames.  The
+    last token of a run is never embedded by the loop; when a known run follows, the prefill embeds it.  A known run at the end costs
+    nothing.  Known frames condition only what comes after them."""
+    n, dev = model.image_seq_len, prompt.device
+    B = known.shape[0]
+    halves = prompt.shape[0] // B
+    runs = segments(pattern)
+    if all(k for k, _, _ in runs):
+        return known.clone()
+    tower = model.transformer
+    cache = tower.new_kv_cache(prompt.shape[0], model.total_seq_len, dev)
+    out = torch.empty(B, len(pattern) * n, dtype=torch.long, device=dev)
+    ids, h = prompt, None
+    for i, (k, f0, nf) in enumerate(runs):
+        lo, hi = f0 * n, (f0 + nf) * n
+        if k:
+            out[:, lo:hi] = known[:, lo:hi]
+            if i == len(runs) - 1:
+                break
+            ids = torch.cat((ids, out[:, lo:hi].repeat(halves, 1)), 1)
+            h = tower.prefill(model._embed_rows(ids, 0), cache)[:, -1, :].contiguous()
+            continue
+        if h is None:  # the sequence starts with unknown frames: the prompt alone, as in a call without known frames
+            h = tower.prefill(model._embed_rows(ids, 0), cache)[:, -1, :].contiguous()
+        toks = sample(model, h, cache, ids.shape[1], filter_thres, temperature, race, trunc, guide, trace, steps=hi - lo)
+        out[:, lo:hi] = torch.cat(toks, dim=-1)
+        if i < len(runs) - 1:
+            ids = torch.cat((ids, out[:, lo:hi].repeat(halves, 1)), 1)
+    return out

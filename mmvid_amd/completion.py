@@ -12,7 +12,7 @@ region of `frames` with a constant (the reference's erase_real uses ones) rather
 """
 import torch
 
-from . import ops, sampling
+from . import artv_sampling, ops, sampling
 
 SHAPES = '[b, T] (whole frames), [b, T, h, w] (token grid) or [b, T, H, W] (pixels)'
 
@@ -126,5 +126,49 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
                     ops.frames_to_u8(dec, out[i:i + step])
             out = out.view(b, T, s, s, 3)
         return out, seq.view(b, T, n)
+    finally:
+        model.train(was_training)
+
+
+@torch.no_grad()
+def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, temperature=1., erase_visual=False, vc_mode=None,
+                  face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None, guidance_drop=sampling.GUIDANCE_DROPS,
+                  negative_text=None, paste=True, _race=None, _trace=None):
+    """Video prediction on the autoregressive (ART-V) model -> (frames_u8 [b, T, H, W, 3] uint8 on the device, tokens [b, T * n] int64).
+
+    `frames`: as for `complete` (fp32 [b, T, 3, H, W] in [0, 1], uint8 [b, T, H, W, 3], or int64 tokens [b, T * n]); only the frames
+    `given` marks are read as known.  `given`: whole frames, [b, T] or [T], bool or uint8; every video may have its own.  A token-grid
+    or pixel mask is refused: the model predicts tokens in raster order, frame after frame, and cannot take a later token of a frame
+    into account.  CAUSALITY: a known frame conditions only the frames that come after it.  Frames generated in front of a known frame
+    do not see it -- [0, 1, 1, 0] generates frame 0 from the text and the visual control alone, then frame 3 from frames 0-2 -- so
+    in-betweening key frames is the BERT's task (`complete`), and prediction from the first frames is this one's.
+
+    The other keywords are those of DALLE.generate_images, which samples (`given=(mask, tokens)`).  The result is decoded once, in
+    slices of `vae._max_frames`; with `paste` and pixel `frames` the known frames are the input's own bytes and not their VQGAN
+    reconstruction (csrc/frames.hip); with token input there are no pixels to paste and the plain byte kernel runs."""
+    T, n, s, f = model.num_targets, model.image_seq_len, model.image_size, model.image_fmap_size
+    b, dev = text.shape[0], text.device
+    mask = artv_sampling.check_frame_mask(given, b, T)  # (before the frames are tokenised)
+    if isinstance(visual, (list, tuple)):  # frames [b, 3, H, W] each, as get_image_tokens takes them
+        visual = torch.stack(list(visual), dim=1) if len(visual) else None
+    was_training = model.training
+    model.eval()
+    try:
+        tokens, real = _frames_to_tokens(model, frames, b)
+        _, seq = model.sample_tokens(text, visual=visual, filter_thres=filter_thres, temperature=temperature, erase_visual=erase_visual,
+                                     vc_mode=vc_mode, face_mode=face_mode, use_cache=use_cache, top_k=top_k, top_p=top_p,
+                                     guidance_scale=guidance_scale, guidance_drop=guidance_drop, negative_text=negative_text,
+                                     given=(mask, tokens.to(dev)), _race=_race, _trace=_trace)
+        flat = seq.reshape(b * T, n)
+        out = torch.empty(b * T, s, s, 3, device=dev, dtype=torch.uint8)
+        grid = mask.to(dev).view(b * T, 1, 1).expand(b * T, f, f).contiguous()
+        step = model.vae._max_frames(s)
+        for i in range(0, b * T, step):
+            dec = model.vae.decode(flat[i:i + step])
+            if paste and real is not None:
+                ops.frames_paste_u8(dec, real[i:i + step], grid[i:i + step], out[i:i + step])
+            else:
+                ops.frames_to_u8(dec, out[i:i + step])
+        return out.view(b, T, s, s, 3), seq.view(b, T * n)
     finally:
         model.train(was_training)

@@ -60,6 +60,7 @@ class DALLE(nn.Module):
         self.num_control_tokens = num_text_tokens + num_visual_tokens
         self.text_seq_len, self.image_seq_len = text_seq_len, image_seq_len
         self.num_visuals, self.num_targets, self.image_fmap_size = num_visuals, num_targets, image_fmap_size
+        self.image_size = vae.image_size
         self.special_token_lut = {'[REL]': 0, '[ST1]': 1, '[ST2]': 2, '[ST3]': 3}
         self.num_special_tokens, self.num_estimation_tokens = 4, 2
         self.special_emb = nn.Embedding(self.num_special_tokens, dim)        # unused in forward (as the reference)
@@ -320,7 +321,7 @@ class DALLE(nn.Module):
     @eval_decorator
     def generate_images(self, text, *, clip=None, visual=None, mask=None, filter_thres=0.5, temperature=1.,
                         erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None,
-                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, _race=None, _trace=None, **kwargs):
+                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, given=None, _race=None, _trace=None, **kwargs):
         """dalle_artv.py:236-304.  use_cache=True (default): the prompt runs once and every sampled token costs one
         incremental step over the per-layer key/value cache; use_cache=False: the reference's algorithm (the whole
         transformer over the growing prefix per token).  Both draw from the same distribution: softmax over the image
@@ -335,48 +336,103 @@ class DALLE(nn.Module):
         lacks what `guidance_drop` names ('text': all pad; 'visual': every slot its pad id) and takes `negative_text` (int64
         [B, text_seq_len]) for its text when given.  top_k / top_p then truncate the guided distribution.  Not accepted with guidance: a
         per-token scale schedule, and a `filter_thres` that removes image classes.  `_trace` (a list, cached path): one dict of clones
-        per token (artv_sampling.sample), through the eager loop with per-token variates."""
+        per token (artv_sampling.sample), through the eager loop with per-token variates.
+
+        `given` = (mask, tokens): video prediction.  mask ([B, T] or [T], bool or uint8) names the known frames of each video, tokens
+        (int64 [B, T * n]) holds them; values under a 0 mask are ignored.  Known frames come back as they are, and every generated frame
+        is conditioned on the known and generated frames BEFORE it (the model is causal: a known frame says nothing to the frames in
+        front of it).  Rows with the same mask run together, one pass through artv_sampling.sample_given per distinct mask; the visual
+        tokens are computed once for the whole batch.  Under guidance both branches carry the same known and drawn tokens.  Known
+        positions draw nothing: `_race` is asked for `tok{j}` of the generated positions j of the target sequence only, `_trace` gets
+        records of those only, and both need one mask for the whole batch."""
+        return self._decode_tokens(*self.sample_tokens(text, visual=visual, filter_thres=filter_thres, temperature=temperature,
+                                                       erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, use_cache=use_cache,
+                                                       top_k=top_k, top_p=top_p, guidance_scale=guidance_scale, guidance_drop=guidance_drop,
+                                                       negative_text=negative_text, given=given, _race=_race, _trace=_trace), clip)
+
+    def _decode_tokens(self, text, tokens, clip=None):
+        """The tail of generate_images: tokens [B, target_seq_len] -> (images, [], None), or (images, clip scores)."""
+        images = self.vae.decode(tokens.reshape(-1, self.image_seq_len))
+        if self.num_targets > 1:
+            images = images.view(-1, self.num_targets, *images.shape[1:])
+        if exists(clip):
+            out = torch.cat((text, tokens + self.num_control_tokens), dim=-1)
+            return images, clip(out[:, :self.text_seq_len], images, return_loss=False)
+        return images, [], None
+
+    @torch.no_grad()
+    @eval_decorator
+    def sample_tokens(self, text, *, visual=None, filter_thres=0.5, temperature=1., erase_visual=False, vc_mode=None, face_mode=None,
+                      use_cache=True, top_k=None, top_p=None, guidance_scale=None, guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None,
+                      given=None, _race=None, _trace=None):
+        """The sampler of generate_images without the decode -> (text [B, text_seq_len], tokens int64 [B, target_seq_len])."""
         tsl = self.text_seq_len
         text = text[:, :tsl]
         B = text.shape[0]
+        groups = None
+        if given is not None:
+            gmask, gtok = artv_sampling.check_given(given, B, self.num_targets, self.image_seq_len, self.num_image_tokens)
+            groups = artv_sampling.group_rows(gmask)
+            if len(groups) > 1 and (_race is not None or _trace is not None):
+                raise ValueError(f'_race / _trace follow one pass through the token loop: {len(groups)} distinct masks in the batch')
+            if not gmask.any():  # nothing known: the call without `given`
+                groups = None
         guide = self._guidance(B, guidance_scale, guidance_drop, negative_text, filter_thres)
         trunc = sampling.check_truncation_artv(top_k, top_p, self.num_image_tokens)
         if _trace is not None and not use_cache:
             raise ValueError('_trace records the token loop over the key/value cache: use_cache=True')
+        if groups is not None and all(all(p) for p, _ in groups):  # everything known: no tower work
+            return text, gtok.to(text.device).clone()
         # visual control tokens (with the erasing the reference applies on every step, dalle_artv.py:464-472) are fixed
         # during sampling: tokenise once
         vis_tok = self._visual_tokens(visual, erase_visual, True, vc_mode, face_mode, None)
-        cl = self.control_seq_len
-        c0, c1 = self._allowed_range(cl)
         scale = None
+        text_c = text
         if guide is not None:  # rows B..2B-1: the unconditional prompt (both branches share the erase and the face region of vis_tok)
             drop, scale = guide[0], self._scale_vector(guide[1], B, text.device)
             text_u, vis_u = sampling.unconditional_inputs(text, vis_tok, drop, negative_text[:, :tsl] if negative_text is not None else None)
             if vis_tok is not None and vis_u is None:
                 vis_u = torch.full_like(vis_tok, -1)
             text, vis_tok = torch.cat((text, text_u), 0), (torch.cat((vis_tok, vis_u), 0) if vis_tok is not None else None)
+        if groups is None:
+            return text_c, self._sample_rows(text, vis_tok, B, None, None, filter_thres, temperature, use_cache, trunc, scale, _race, _trace)
+        gtok = gtok.to(text.device)
+        parts = []
+        for pattern, rows in groups:
+            if len(groups) == 1:
+                t, v, s, g = text, vis_tok, scale, gtok
+            else:  # this mask's rows of the batch (guided: of both halves)
+                idx = torch.tensor(rows, dtype=torch.long, device=text.device)
+                sel = idx if guide is None else torch.cat((idx, idx + B))
+                t, v, g = text.index_select(0, sel), (vis_tok.index_select(0, sel) if vis_tok is not None else None), gtok.index_select(0, idx)
+                s = scale.index_select(0, idx).contiguous() if scale is not None else None
+            parts.append((rows, self._sample_rows(t, v, len(rows), pattern, g, filter_thres, temperature, use_cache, trunc, s, _race, _trace)))
+        return text_c, artv_sampling.scatter_rows(parts, B)
+
+    def _sample_rows(self, text, vis_tok, B, pattern, known, filter_thres, temperature, use_cache, trunc, scale, _race, _trace):
+        """Tokens [B, target_seq_len] for prompts that share one frame mask `pattern` (None: nothing known).  text / vis_tok: B rows, or
+        [conditional; unconditional] = 2B rows with `scale`."""
         rows = text.shape[0]
-        toks = []
+        cl = self.control_seq_len
+        c0, c1 = self._allowed_range(cl)
         if use_cache:
-            cache = self.transformer.new_kv_cache(rows, self.total_seq_len, text.device)
             prompt = torch.cat(self._prompt_ids(text, vis_tok), 1)  # <bos> text visual: positions 0 .. cl
+            if pattern is not None:
+                return artv_sampling.sample_given(self, prompt, pattern, known, filter_thres, temperature, _race, trunc, scale, _trace)
+            cache = self.transformer.new_kv_cache(rows, self.total_seq_len, text.device)
             h = self.transformer.prefill(self._embed_rows(prompt, 0), cache)[:, -1, :].contiguous()
-            toks = artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc, scale, _trace)
-        else:
-            image = torch.empty(rows, 0, dtype=torch.long, device=text.device)
-            for step in range(self.target_seq_len):
+            return torch.cat(artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc, scale, _trace), dim=-1)
+        n = self.image_seq_len
+        image = torch.empty(rows, 0, dtype=torch.long, device=text.device)
+        runs = artv_sampling.segments(pattern) if pattern is not None else [(False, 0, self.num_targets)]
+        for k, f0, nf in runs:
+            if k:  # known frames are appended, nothing is drawn
+                image = torch.cat((image, known[:, f0 * n:(f0 + nf) * n].repeat(rows // B, 1)), dim=-1)
+                continue
+            for step in range(f0 * n, (f0 + nf) * n):
                 hidden = self._hidden(text, vis_tok, image)[0]
                 logits = self._logits_rows(hidden[:, -1, :].contiguous(), (c0, c1))
-                sample = self._draw(logits[:B], filter_thres, temperature, _race, f'tok{step}', trunc, logits[B:] if guide is not None else None,
+                sample = self._draw(logits[:B], filter_thres, temperature, _race, f'tok{step}', trunc, logits[B:] if scale is not None else None,
                                     scale)
-                toks.append(sample)
-                image = torch.cat((image, sample if guide is None else sample.repeat(2, 1)), dim=-1)  # (both halves carry the same tokens)
-        text = text[:B]
-        img_seq = torch.cat(toks, dim=-1).reshape(-1, self.image_seq_len)
-        images = self.vae.decode(img_seq)
-        if self.num_targets > 1:
-            images = images.view(-1, self.num_targets, *images.shape[1:])
-        if exists(clip):
-            out = torch.cat((text, torch.cat(toks, dim=-1) + self.num_control_tokens), dim=-1)
-            return images, clip(out[:, :tsl], images, return_loss=False)
-        return images, [], None
+                image = torch.cat((image, sample if scale is None else sample.repeat(2, 1)), dim=-1)  # (both halves carry the same tokens)
+        return image[:B]

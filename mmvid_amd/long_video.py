@@ -203,6 +203,68 @@ def generate_long(model, text, *, visual=None, mode='long', t_repeat=10, t_overl
         model.train(was_training)
 
 
+def artv_sampler(model, text, *, visual=None, _race=None, **sampling_kw):
+    """The `sample` of `run` on an ART-V model (dalle_artv.DALLE, in eval mode) for mode 'long': the last `t_overlap` frames of
+    `preserve` (the previous clip) are the known first frames of the next clip, which enter through the prefill
+    (DALLE.sample_tokens(given=...)); the first clip is a plain call.  `sampling_kw`: the sampling keywords of generate_images.  The
+    interp modes hand a window frames that lie AFTER the ones it generates, which a causal model cannot use: ValueError."""
+    b = text.shape[0]
+    T, n = model.num_targets, model.image_seq_len
+
+    def sample(level, chunk, rows, preserve, long_mode, overlap):
+        if long_mode != 'long':
+            raise ValueError(f'long_mode={long_mode!r}: an ART-V model extrapolates only (mode "long"); interpolation conditions on later frames')
+        index = torch.arange(rows[0], rows[1], device=text.device) % b
+        whole = rows[1] - rows[0] == b and rows[0] % b == 0
+        t = text if whole else text.index_select(0, index)
+        v = visual if whole or visual is None else visual.index_select(0, index.to(visual.device))
+        given = None
+        if preserve is not None:
+            o = int(overlap)
+            mask = torch.tensor([1] * o + [0] * (T - o), dtype=torch.uint8)
+            tokens = torch.zeros(rows[1] - rows[0], T * n, dtype=torch.long, device=preserve.device)
+            tokens[:, :o * n] = preserve.reshape(rows[1] - rows[0], T, n)[:, T - o:].reshape(-1, o * n)
+            given = (mask, tokens)
+        race = None if _race is None else (lambda name, shape: _race(f'L{level}c{chunk}/{name}', shape))
+        return model.sample_tokens(t, visual=v, given=given, _race=race, **sampling_kw)[1]
+
+    return sample
+
+
+@torch.no_grad()
+def generate_long_artv(model, text, *, visual=None, mode='long', t_repeat=10, t_overlap=1, decode=True, max_rows=MAX_ROWS, trace=None,
+                       _race=None, **sampling_kw):
+    """Long extrapolation on an ART-V model -> (frames_u8 [b, F, H, W, 3] uint8 on the device, or None without `decode`; tokens
+    [b, F, image_seq_len] int64): clip k + 1 continues the last `t_overlap` frames of clip k (plan / run of mode 'long', one window per
+    level).  The interp modes raise ValueError: they need the future.  `sampling_kw`: the sampling keywords of generate_images;
+    `_race(name, shape)` supplies the variates, names prefixed with 'L{level}c{chunk}/'.  `trace` (a list): the dicts of `run`."""
+    if mode in MODES and mode != 'long':
+        raise ValueError(f'mode={mode!r}: an ART-V model extrapolates only (mode "long"); the interp modes condition a window on frames '
+                         'that come after the ones it generates')
+    T, n = model.num_targets, model.image_seq_len
+    levels = plan(mode, T, t_repeat, t_overlap)
+    b, dev = text.shape[0], text.device
+    if isinstance(visual, (list, tuple)):  # frames [b, 3, H, W] each, as get_image_tokens takes them
+        visual = torch.stack(list(visual), dim=1) if len(visual) else None
+    was_training = model.training
+    model.eval()
+    try:
+        sample = artv_sampler(model, text, visual=visual, _race=_race, **sampling_kw)
+        tokens = run(levels, sample, b=b, num_targets=T, mask_id=-1, max_rows=max_rows, trace=trace)
+        frames = None
+        if decode:
+            F, s = tokens.shape[1], model.image_size
+            flat = tokens.view(b * F, n)
+            frames = torch.empty(b * F, s, s, 3, device=dev, dtype=torch.uint8)
+            step = model.vae._max_frames(s)
+            for i in range(0, b * F, step):
+                ops.frames_to_u8(model.vae.decode(flat[i:i + step]), frames[i:i + step])
+            frames = frames.view(b, F, s, s, 3)
+        return frames, tokens
+    finally:
+        model.train(was_training)
+
+
 def save(frames_u8, path, video_format='gif', fps=4):
     """One video [F, H, W, 3] uint8 (device or host; `generate_long(...)[0][i]`) -> `<path>.gif`, or `<path>.mp4` (Motion-JPEG,
     data.write_mjpeg_mp4) with video_format='mp4'.  The bytes are written as they are.  Returns the file name, as
