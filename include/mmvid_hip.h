@@ -699,9 +699,11 @@ int mmvid_prof_end(double* ms, int64_t* sampled, double* flops, int64_t* launche
 
 /* ---- OpenAI CLIP around the towers (csrc/clip.hip; mmvid_amd/clip_model.py).  Inference only.
  * patchify: utils/utils.py:66-71 (F.interpolate nearest to R, (x - mean) / std) + clip_model.py:274 (conv1 as a GEMM operand).
- *   frames fp32 [N,3,S,S] -> bf16 [N*(R/P)^2, 3*P*P], columns (c, ky, kx) = visual.conv1.weight.reshape(width, 3*P*P).
+ *   frames fp32 [N,3,S,S] -> bf16 [N*(R/P)^2, Kp], Kp = 3*P*P rounded up to a multiple of 64 (= 3*P*P when P is a multiple of 8).
+ *   Columns j < 3*P*P are (c, ky, kx) = visual.conv1.weight.reshape(width, 3*P*P); columns [3*P*P, Kp) are +0.0, so a weight
+ *   operand [width, Kp] with a zero tail gives the same products and no K tile of the GEMM is ragged.
  *   normalize=1: frames in [0, 1]; src = min(floor(dst * ((float)S / R)), S - 1) (ATen's nearest rule), then CLIP's mean / std.
- *   normalize=0: frames already at R and normalised (S must equal R).  P a multiple of 8. */
+ *   normalize=0: frames already at R and normalised (S must equal R).  Any P >= 1 (at most 16384) that divides R. */
 int mmvid_clip_patchify(const float* frames, int N, int S, int R, int P, int normalize, void* out_bf16, void* stream);
 /* clip_model.py:275-284: out [N,T,E] = ln_pre([class_emb | patch_feat rows of the frame] + pos[T,E]); patch_feat [N*(T-1), E]
  * fp32 (the patch GEMM's result).  E a multiple of 256, at most 1024. */

@@ -12,7 +12,7 @@ from . import _lib, ops
 from .clip_tower import OpenAICLIPTransformer, _Holder, _ln_params
 
 f32, bf16 = torch.float32, torch.bfloat16
-IMAGE_SLICE = 256  # frames per pass through the visual tower (bounds the tower's scratch; results do not depend on it)
+IMAGE_SLICE = 256  # frames per pass through the visual tower at 50 positions (bounds the tower's scratch: frames_per_pass; results do not depend on it)
 
 
 def _param(t):
@@ -52,9 +52,9 @@ class CLIP(nn.Module):
         super().__init__()
         if isinstance(vision_layers, (tuple, list)):
             raise NotImplementedError('CLIP with a ModifiedResNet image tower (RN50 family) is not implemented: ViT checkpoints only')
-        if vision_patch_size % 8 or image_resolution % vision_patch_size:
+        if vision_patch_size < 1 or image_resolution % vision_patch_size:
             raise NotImplementedError(f'patch size {vision_patch_size} / resolution {image_resolution}: the patch kernel needs a '
-                                      'patch size that is a multiple of 8 and divides the resolution')
+                                      'patch size that divides the resolution')
         self.visual = VisualTransformer(image_resolution, vision_patch_size, vision_width, vision_layers, vision_width // 64, embed_dim)
         text_tower = _tower(context_length, 'openai_clip_text', True, transformer_width, transformer_layers, transformer_heads)
         self.transformer = text_tower.transformer
@@ -115,11 +115,17 @@ class CLIP(nn.Module):
                                'its parameters and inputs (requires_grad_(False))')
 
     def _conv_weight(self):
-        """bf16 copy of conv1.weight as the patch GEMM's [width, 3*P*P] operand, rebuilt when the parameter changes."""
+        """bf16 copy of conv1.weight as the patch GEMM's [width, Kp] operand (columns beyond 3*P*P zero: see patch_columns), rebuilt
+        when the parameter changes."""
         w = self.visual.conv1.weight
         key = (w._version, w.data_ptr(), w.device)
         if self._conv_key != key:
-            self._conv_bf16 = ops.cast_bf16(w.detach().contiguous().view(w.shape[0], -1))
+            flat = ops.cast_bf16(w.detach().contiguous().view(w.shape[0], -1))
+            Kp = patch_columns(self._shape['P'])
+            if Kp != flat.shape[1]:
+                flat, dense = torch.zeros(w.shape[0], Kp, device=w.device, dtype=bf16), flat
+                flat[:, :dense.shape[1]] = dense
+            self._conv_bf16 = flat
             self._conv_key = key
         return self._conv_bf16
 
@@ -138,7 +144,7 @@ class CLIP(nn.Module):
         vis = self.visual
         n, E, T = image.shape[0], vis.class_embedding.shape[0], (R // P)**2 + 1
         patches = patchify(image, R, P, normalize)
-        feat = ops.gemm(patches, self._conv_weight(), out_dtype=f32)  # conv1 (stride = kernel = P, no bias): [n*G*G, 3*P*P] x [E, 3*P*P]^T
+        feat = ops.gemm(patches, self._conv_weight(), out_dtype=f32)  # conv1 (stride = kernel = P, no bias): [n*G*G, Kp] x [E, Kp]^T
         x = torch.empty(n, T, E, device=image.device, dtype=f32)
         _lib.call('mmvid_clip_image_assemble', ops._p(feat), ops._p(vis.class_embedding), ops._p(vis.positional_embedding),
                   ops._p(vis.ln_pre.weight), ops._p(vis.ln_pre.bias), 1e-5, n, T, E, ops._p(x), ops._stream())
@@ -146,14 +152,15 @@ class CLIP(nn.Module):
 
     def _image_features(self, image, normalize, l2):
         """frames [N,3,S,S] -> [N, embed_dim] fp32.  normalize: frames in [0, 1] at any S (clip_similarity's resize + normalise);
-        otherwise encode_image's input (normalised, S == R).  Slices of IMAGE_SLICE frames: every kernel is row-independent."""
+        otherwise encode_image's input (normalised, S == R).  Slices of frames_per_pass frames: every kernel is row-independent."""
         image = self._check_image(image, normalize)
         N, D = image.shape[0], self._shape['D']
         vis = self.visual
         E = vis.class_embedding.shape[0]
         out = torch.empty(N, D, device=image.device, dtype=f32)
-        for n0 in range(0, N, IMAGE_SLICE):
-            n = min(IMAGE_SLICE, N - n0)
+        per = frames_per_pass((self._shape['R'] // self._shape['P'])**2 + 1)
+        for n0 in range(0, N, per):
+            n = min(per, N - n0)
             x = self._image_sequence(image[n0:n0 + n], normalize)
             y, _ = vis.tower._run_forward(x, keep=False)
             _lib.call('mmvid_clip_pool_project', ops._p(y), n, y.shape[1], E, None, ops._p(vis.ln_post.weight), ops._p(vis.ln_post.bias),
@@ -187,12 +194,24 @@ class CLIP(nn.Module):
         return out
 
 
+def patch_columns(P):
+    """Kp: the patch matrix's row length, 3*P*P rounded up to a multiple of 64 (3*P*P itself when P is a multiple of 8)."""
+    return -(-3 * P * P // 64) * 64
+
+
+def frames_per_pass(T):
+    """Frames per pass through a visual tower of T = G*G + 1 positions: the rows of IMAGE_SLICE frames at ViT-B/32's T = 50, so the
+    tower's scratch stays where it is at any grid (256 frames at T = 50, 49 at 257, 22 at 577)."""
+    return max(1, (IMAGE_SLICE * 50) // T)
+
+
 def patchify(frames, R, P, normalize):
-    """frames fp32 [N,3,S,S] -> bf16 [N*(R/P)^2, 3*P*P], columns (c, ky, kx).  normalize: frames in [0, 1], resized to R with
-    F.interpolate's `nearest` rule and normalised with CLIP's mean / std (utils/utils.py:66-71); otherwise taken as they are (S == R)."""
+    """frames fp32 [N,3,S,S] -> bf16 [N*(R/P)^2, Kp], columns (c, ky, kx), then zeros up to Kp = patch_columns(P).  normalize: frames
+    in [0, 1], resized to R with F.interpolate's `nearest` rule and normalised with CLIP's mean / std (utils/utils.py:66-71);
+    otherwise taken as they are (S == R)."""
     frames = ops._chk(frames, f32, 'frames')
     N, S = frames.shape[0], frames.shape[2]
-    out = torch.empty(N * (R // P)**2, 3 * P * P, device=frames.device, dtype=bf16)
+    out = torch.empty(N * (R // P)**2, patch_columns(P), device=frames.device, dtype=bf16)
     if N:
         _lib.call('mmvid_clip_patchify', ops._p(frames), N, S, R, P, int(normalize), ops._p(out), ops._stream())
     return out
@@ -222,7 +241,7 @@ def build_model(state_dict):
 
 
 def load(path, device='cuda'):
-    """The ViT CLIP of an OpenAI TorchScript archive (e.g. ViT-B-32.pt) -- what the reference gets from torch.jit.load(path)
+    """The ViT CLIP of an OpenAI TorchScript archive (ViT-B-32.pt, ViT-B-16.pt, ViT-L-14.pt, ViT-L-14-336px.pt) -- what the reference gets from torch.jit.load(path)
     (utils_eval.py:241) -- on `device`."""
     archive = torch.jit.load(path, map_location='cpu')
     return build_model(archive.state_dict()).to(device)

@@ -2,7 +2,8 @@
 // 399-414 CLIP.encode_text, 416-432 CLIP.forward) and the frame preprocessing of utils/utils.py:62-85 clip_similarity.
 // The towers themselves are mmvid_tower_forward (tower.hip), the patch embedding is mmvid_gemm_bf16 (gemm.hip).
 //
-//   patchify        frames [N,3,S,S] fp32 -> (nearest resize to R, (x - mean) / std) -> bf16 patch matrix [N*G*G, 3*P*P]
+//   patchify        frames [N,3,S,S] fp32 -> (nearest resize to R, (x - mean) / std) -> bf16 patch matrix [N*G*G, Kp]
+//                   (Kp = 3*P*P rounded up to a multiple of 64, zero pad columns: the patch GEMM's K never has a ragged tile)
 //   image_assemble  patch features [N*G*G, E] fp32 -> [class | patches] + positional_embedding -> ln_pre -> [N, G*G+1, E] fp32
 //   text_embed      ids [B,L] -> token_embedding rows + positional_embedding [B,L,E] fp32, and argmax(ids) per row (first maximum)
 //   pool_project    one row per sequence -> ln_post / ln_final -> @ proj [E,D] -> (optional) L2 normalisation -> [B,D] fp32
@@ -43,6 +44,43 @@ __global__ __launch_bounds__(256) void clip_patchify_kernel(const float* __restr
     uint4 o;
     o.x = pack_bf2(v[0], v[1]), o.y = pack_bf2(v[2], v[3]), o.z = pack_bf2(v[4], v[5]), o.w = pack_bf2(v[6], v[7]);
     *reinterpret_cast<uint4*>(out + row * (3 * P * P) + col) = o;
+}
+
+// Any patch size: rows of Kp = 3*P*P rounded up to a multiple of 64 columns, columns [3*P*P, Kp) +0.0.  One thread per 8 consecutive
+// columns of one row (one 16-byte store; Kp % 8 == 0, so a store never crosses a row): the first column is decoded into (c, ky, kx)
+// by division, the next seven by carrying (kx -> ky -> c), and c >= 3 marks a pad column.  Each value is clip_patchify_kernel's
+// expression, so where both kernels apply they store the same bytes.
+__global__ __launch_bounds__(256) void clip_patchify_padded_kernel(const float* __restrict__ x, int64_t total, int S, int R, int P, int G,
+                                                                   int Kp, int normalize, float scale, bf16_t* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int cols8 = Kp / 8;
+    const int64_t row = t / cols8;
+    const int col = (int)(t - row * cols8) * 8;
+    int c = col / (P * P);
+    const int rem = col - c * P * P;
+    int ky = rem / P, kx = rem - ky * P;
+    const int64_t n = row / (G * G);
+    const int p = (int)(row - n * G * G), py = p / G, px = p - py * G;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        v[j] = 0.f;
+        if (c < 3) {
+            const int y = py * P + ky, xx = px * P + kx;
+            const int sy = normalize ? min((int)floorf((float)y * scale), S - 1) : y;
+            const int sx = normalize ? min((int)floorf((float)xx * scale), S - 1) : xx;
+            v[j] = x[((n * 3 + c) * S + sy) * (int64_t)S + sx];
+            if (normalize) v[j] = __fdiv_rn(__fsub_rn(v[j], kMean[c]), kStd[c]);
+        }
+        if (++kx == P) {
+            kx = 0;
+            if (++ky == P) ky = 0, ++c;
+        }
+    }
+    uint4 o;
+    o.x = pack_bf2(v[0], v[1]), o.y = pack_bf2(v[2], v[3]), o.z = pack_bf2(v[4], v[5]), o.w = pack_bf2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(out + row * Kp + col) = o;
 }
 
 // LayerNorm of NV float4 per lane (E = 256 * NV) held by one wave; y = (v - mean) * rstd * w + b
@@ -225,14 +263,21 @@ int check_width(int E, const char* what) {
 
 extern "C" int mmvid_clip_patchify(const float* frames, int N, int S, int R, int P, int normalize, void* out_bf16, void* stream) {
     MMVID_REQUIRE(frames && out_bf16, "clip_patchify: null pointer");
-    MMVID_REQUIRE(N > 0 && S > 0 && P > 0 && P % 8 == 0 && R > 0 && R % P == 0, "clip_patchify: bad sizes N=%d S=%d R=%d P=%d "
-                  "(P a multiple of 8 dividing R)", N, S, R, P);
+    MMVID_REQUIRE(N > 0 && S > 0 && P > 0 && P <= 16384 && R > 0 && R % P == 0, "clip_patchify: bad sizes N=%d S=%d R=%d P=%d "
+                  "(P at most 16384, dividing R)", N, S, R, P);
     MMVID_REQUIRE(normalize || S == R, "clip_patchify: normalize=0 takes frames already at the input resolution (S=%d, R=%d)", S, R);
     const int G = R / P;
-    const int64_t total = (int64_t)N * G * G * (3 * P * P / 8);
     const float scale = (float)S / (float)R;
-    hipLaunchKernelGGL(clip_patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames, total, S,
-                       R, P, G, normalize, scale, (bf16_t*)out_bf16);
+    if (P % 8 == 0) {  // 3*P*P is a multiple of 64: no pad columns
+        const int64_t total = (int64_t)N * G * G * (3 * P * P / 8);
+        hipLaunchKernelGGL(clip_patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames, total,
+                           S, R, P, G, normalize, scale, (bf16_t*)out_bf16);
+    } else {
+        const int Kp = (3 * P * P + 63) / 64 * 64;
+        const int64_t total = (int64_t)N * G * G * (Kp / 8);
+        hipLaunchKernelGGL(clip_patchify_padded_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames,
+                           total, S, R, P, G, Kp, normalize, scale, (bf16_t*)out_bf16);
+    }
     MMVID_LAUNCH_CHECK("clip_patchify");
     return MMVID_OK;
 }

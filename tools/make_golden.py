@@ -9,7 +9,7 @@ layout), and the reference's outputs.  Run:
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [case ...]
 
 Cases: vq vqgan_tiny vqgan_full vqgan_full16 vqgan_full16_refinit tower tower12 bert_tiny bert_tiny_visual bert_negvc bert_negvc_visual bert_flm bert_flm_bottleneck artv_tiny mask_predict
-       frontend mask_predict_race clip_vit2 clip_vit12 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd long_video
+       frontend mask_predict_race clip_vit2 clip_vit12 clip_p14_tiny clip_vitl14_2 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd long_video
 """
 import json
 import os
@@ -803,10 +803,15 @@ CLIP_DESCRIPTIONS = [  # clip_vit*: one caption longer than the 77-token context
 ]
 
 
-def _clip_case(name, layers, seed):
-    """OpenAI CLIP ViT-B/32 (clip_model.py:298-436) with `layers` layers in both towers, synthetic weights of `seed`, logit_scale at
-    its initial log(1/0.07): encode_image / encode_text / forward, utils/utils.py:62-85 clip_similarity (its own lines, .cuda() the
-    identity on this CPU-only host) and the ln_final token features of utils_train.py:264-274."""
+CLIP_B32 = lambda layers: (512, 224, layers, 768, 32, 77, 49408, 512, 8, layers)  # noqa: E731  (CLIP's constructor arguments)
+
+
+def _clip_case(name, layers, seed, shape=None, small=128):
+    """OpenAI CLIP (clip_model.py:298-436) of constructor arguments `shape` (default: ViT-B/32 with `layers` layers in both towers),
+    synthetic weights of `seed`, logit_scale at its initial log(1/0.07): encode_image / encode_text / forward, utils/utils.py:62-85
+    clip_similarity (its own lines, .cuda() the identity on this CPU-only host) and the ln_final token features of
+    utils_train.py:264-274.  Inputs: 6 frames of `small`^2 in [0, 1] (resized by clip_similarity's own lines) and 2 normalised
+    frames at the model's resolution R; their seeds' names carry the sizes."""
     import types
     sys.modules.setdefault('ftfy', types.SimpleNamespace(fix_text=lambda t: t))
     from mmvid_pytorch.tokenizer import SimpleTokenizer
@@ -814,20 +819,22 @@ def _clip_case(name, layers, seed):
     import utils.utils as ref_utils
     from utils.utils import clip_similarity
     ref_utils.F = torch.nn.functional  # utils/utils.py uses F without importing it (the drivers' namespace has it)
-    clip = CLIP(512, 224, layers, 768, 32, 77, 49408, 512, 8, layers)
+    shape = tuple(shape or CLIP_B32(layers))
+    R, ctx = shape[1], shape[5]
+    clip = CLIP(*shape)
     man = load_synth(clip, seed)
     with torch.no_grad():
         clip.logit_scale.fill_(float(np.log(1 / 0.07)))
     clip.eval()
-    clip.input_resolution = torch.tensor(224)  # the TorchScript archive's attributes that clip_similarity reads
-    clip.context_length = torch.tensor(77)
+    clip.input_resolution = torch.tensor(R)  # the TorchScript archive's attributes that clip_similarity reads
+    clip.context_length = torch.tensor(ctx)
     tok = SimpleTokenizer()
-    text = tok.tokenize(CLIP_DESCRIPTIONS, 77, truncate_text=True)
-    frames = synth_input('clip_frames128', (6, 3, 128, 128), seed, 'uniform')
-    frames224 = synth_input('clip_frames224', (2, 3, 224, 224), seed)  # already normalised: encode_image's own input
+    text = tok.tokenize(CLIP_DESCRIPTIONS, ctx, truncate_text=True)
+    frames = synth_input(f'clip_frames{small}', (6, 3, small, small), seed, 'uniform')
+    frames224 = synth_input(f'clip_frames{R}', (2, 3, R, R), seed)  # already normalised: encode_image's own input
     mean = torch.tensor([0.48145466, 0.4578275, 0.40821073])[:, None, None]
     std = torch.tensor([0.26862954, 0.26130258, 0.27577711])[:, None, None]
-    pre = (torch.nn.functional.interpolate(frames, (224, 224)) - mean) / std
+    pre = (torch.nn.functional.interpolate(frames, (R, R)) - mean) / std
     images = torch.cat([pre, frames224])
     cuda = torch.Tensor.cuda
     torch.Tensor.cuda = lambda t, *a, **k: t
@@ -841,8 +848,11 @@ def _clip_case(name, layers, seed):
         sims = [clip_similarity(clip, tok, frames[3 * v:3 * v + 3], [CLIP_DESCRIPTIONS[v]]) for v in range(2)]
     finally:
         torch.Tensor.cuda = cuda
-    save(name, meta=dict(seed=seed, layers=layers, descriptions=CLIP_DESCRIPTIONS, logit_scale=float(np.log(1 / 0.07)),
-                         similarity='frames[3v:3v+3] against descriptions[v], v = 0, 1'),
+    meta = dict(seed=seed, layers=layers, descriptions=CLIP_DESCRIPTIONS, logit_scale=float(np.log(1 / 0.07)),
+                similarity='frames[3v:3v+3] against descriptions[v], v = 0, 1')
+    if shape != CLIP_B32(layers):  # (the ViT-B/32 cases keep the meta they were written with)
+        meta.update(shape=list(shape), small=small)
+    save(name, meta=meta,
          manifest=man, text=text, encode_image=img, encode_text=txt, logits_per_image=lpi, logits_per_text=lpt,
          similarity=np.stack(sims), token_features_s=feats[:, :, ::8], pool_index=text.argmax(-1))
 
@@ -853,6 +863,16 @@ def case_clip_vit2():
 
 def case_clip_vit12():
     _clip_case('clip_vit12', 12, 31)
+
+
+def case_clip_p14_tiny():
+    """Patch 14 at the smallest size: 16 patches of 588 columns (padded to 640 by the patch kernel), T = 17, width 256."""
+    _clip_case('clip_p14_tiny', 2, 37, shape=(256, 56, 2, 256, 14, 77, 49408, 256, 4, 2), small=40)
+
+
+def case_clip_vitl14_2():
+    """ViT-L/14's widths (visual 1024 / 16 heads, text 768 / 12 heads, embed 768) with 2 layers per tower, clip_vit2's inputs."""
+    _clip_case('clip_vitl14_2', 2, 41, shape=(768, 224, 2, 1024, 14, 77, 49408, 768, 12, 2))
 
 
 # ---- RoBERTa (--fixed_language_model roberta-large): transformers' RobertaTokenizer / RobertaModel, the reference's own
@@ -1091,7 +1111,8 @@ CASES = dict(vq=case_vq, vqgan_tiny=case_vqgan_tiny, vqgan_full=case_vqgan_full,
              bert_tiny=case_bert_tiny, bert_tiny_visual=case_bert_tiny_visual, bert_negvc=case_bert_negvc, bert_negvc_visual=case_bert_negvc_visual, bert_flm=case_bert_flm,
              bert_flm_bottleneck=case_bert_flm_bottleneck, artv_tiny=case_artv_tiny,
              mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race,
-             clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12, roberta_tokenizer=case_roberta_tokenizer, roberta_tiny=case_roberta_tiny,
+             clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12, clip_p14_tiny=case_clip_p14_tiny,
+             clip_vitl14_2=case_clip_vitl14_2, roberta_tokenizer=case_roberta_tokenizer, roberta_tiny=case_roberta_tiny,
              roberta_large24=case_roberta_large24, fvd_prd=case_fvd_prd, long_video=case_long_video)
 
 if __name__ == '__main__':
