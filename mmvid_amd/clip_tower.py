@@ -17,7 +17,32 @@ TOWER_SHAPES = {  # which_model -> (width, layers, heads), clip_model.py:538-541
     'openai_clip_visual': (768, 12, 12),
     'openai_clip_text': (512, 12, 8),
 }
+MAX_WIDTH = 1024  # the widest tower the kernels take (csrc/tower.hip: E == 64 H <= 1024): ViT-L/14's visual tower; ViT-H is 1280
 MATRIX_KEYS = ('attn.in_proj_weight', 'attn.out_proj.weight', 'mlp.c_fc.weight', 'mlp.c_proj.weight')
+
+
+def check_tower_width(width, source):
+    """Refuse, with the limit in the message, a tower width the kernels do not take.  `source`: where the number came from."""
+    if width <= 0 or width % 64:
+        raise ValueError(f'{source}: tower width {width} is not a multiple of 64 (the attention kernels take heads of 64: heads = width / 64)')
+    if width > MAX_WIDTH:
+        raise ValueError(f'{source}: tower width {width} is above {MAX_WIDTH}, the widest tower the kernels take '
+                         '(ViT-L/14 visual towers are 1024 wide; ViT-H and larger are not supported)')
+
+
+def tower_shape_of(sd, which_model, source='checkpoint'):
+    """(width, layers, heads) of one tower of an OpenAI CLIP state dict, as clip_model.py:461-512 reads them: the number of
+    `[visual.]transformer.resblocks.N.attn.in_proj_weight` keys and their width; heads = width / 64."""
+    prefix = 'transformer.resblocks.' if which_model == 'openai_clip_text' else 'visual.transformer.resblocks.'
+    keys = [k for k in sd if k.startswith(prefix) and k.endswith('.attn.in_proj_weight')]
+    if not keys:
+        raise ValueError(f'{source}: no {prefix}N.attn.in_proj_weight in the archive, so it holds no tower for {which_model!r} '
+                         '(a ResNet CLIP archive has no visual transformer: only ViT archives are supported; '
+                         'its text tower is which_transformer=\'openai_clip_text\')')
+    layers = len({int(k[len(prefix):].split('.')[0]) for k in keys})
+    width = int(sd[keys[0]].shape[1])
+    check_tower_width(width, f'{source} ({which_model})')
+    return width, layers, width // 64
 
 
 class _Holder(nn.Module):
@@ -110,11 +135,11 @@ class DecodeSession:
                       ops._p(self.cache), self.cache.shape[2], ops._p(self.pos), 0, 1, ops._p(self.ws), ops._stream())  # (advances pos itself)
             return
         Lmax = self.cache.shape[2]
-        if self.fused and E <= 768:
+        if self.fused and (E <= 768 or E == 1024):
             # slices of up to 64 sequences through the decode kernels of csrc/decode.hip (3..64 rows: the linear layers on the matrix pipe,
             # the weights streamed once per slice; the M = B corner of the training GEMM took 2.2 ms per token at batch 16); the last
             # slice's last launch advances the position
-            per = 64 if E in (512, 768) else 16  # (the matrix-pipe linear layers are instantiated for the CLIP widths; others: 16 rows)
+            per = 64 if E in (512, 768, 1024) else 16  # (the matrix-pipe linear layers are instantiated for the CLIP widths; others: 16 rows)
             for b0 in range(0, B, per):
                 nb = min(per, B - b0)
                 cfg = self.cfg if nb == B else self._slice_cfgs.setdefault(nb, self.tower._cfg(nb, Lmax))
@@ -195,11 +220,26 @@ class DecodeSession:
 
 class OpenAICLIPTransformer(nn.Module):
     def __init__(self, seq_len=0, which_model='openai_clip_text', model_path=None, causal=True, mask_type='causal',
-                 mask_kwargs=None, layers=None, width=None, heads=None):
+                 mask_kwargs=None, layers=None, width=None, heads=None, model_dim=None):
+        """model_path: the tower's (width, layers, heads) are the archive's (clip_model.py:535-543 builds whatever the file holds);
+        an explicit `layers` keeps the first `layers` blocks.  model_dim: the embedding width of the model around the tower (BERT /
+        DALLE pass their `dim`), checked against the tower's when that came from an archive or an explicit `width`."""
         super().__init__()
         if not which_model.startswith('openai_clip'):
             raise NotImplementedError(which_model)  # as dalle_bert.py:406-407
         w, l, h = TOWER_SHAPES[which_model]
+        sd, source = None, f'width={width}'
+        if model_path is not None:
+            sd = torch.jit.load(model_path, map_location='cpu').state_dict()
+            source = f'checkpoint {os.path.basename(str(model_path))}'
+            cw, cl, ch = tower_shape_of(sd, which_model, source)
+            if width is not None and width != cw:
+                raise ValueError(f'width={width} was asked for, but the {which_model} tower of {source} is {cw} wide')
+            if layers is not None and layers > cl:
+                raise ValueError(f'layers={layers} were asked for, but the {which_model} tower of {source} has {cl}')
+            width, layers, heads = cw, layers or cl, heads or ch
+        if model_dim is not None and width is not None and model_dim != width:
+            raise ValueError(f'dim={model_dim} does not match the tower: {source} gives a {which_model} tower {width} wide; pass dim={width}')
         self.width, self.layers, self.heads = width or w, layers or l, heads or h
         self.debug_keep_saved = False
         assert self.width == 64 * self.heads, 'head_dim must be 64 (CLIP towers)'
@@ -208,7 +248,7 @@ class OpenAICLIPTransformer(nn.Module):
         self.transformer = _TowerParams(self.width, self.layers)
         self.mask_spec = self.build_attention_mask(seq_len, mask_type, **(mask_kwargs or {})) if causal else None
         if model_path is not None:
-            self.load_clip_checkpoint(model_path, which_model)
+            self.load_clip_checkpoint(model_path, which_model, sd)
         self._shadow = None  # flat bf16 copy of the matrix weights
         self._shadow_key = None
         self._scratch = None
@@ -240,11 +280,14 @@ class OpenAICLIPTransformer(nn.Module):
             m[r, :c] = float('-inf')
         return m
 
-    def load_clip_checkpoint(self, path, which_model):
-        """clip_model.py:535-559: pull one tower out of OpenAI's TorchScript archive (fp16 weights -> fp32)."""
-        sd = torch.jit.load(path, map_location='cpu').state_dict()
+    def load_clip_checkpoint(self, path, which_model, sd=None):
+        """clip_model.py:535-559: pull one tower out of OpenAI's TorchScript archive (fp16 weights -> fp32); of a deeper tower the
+        first self.layers blocks.  sd: the archive's state dict where the caller has read it already."""
+        if sd is None:
+            sd = torch.jit.load(path, map_location='cpu').state_dict()
         prefix = 'transformer.' if which_model == 'openai_clip_text' else 'visual.transformer.'
-        own = {k[len(prefix):]: v.float() for k, v in sd.items() if k.startswith(prefix + 'resblocks.')}
+        own = {k[len(prefix):]: v.float() for k, v in sd.items()
+               if k.startswith(prefix + 'resblocks.') and int(k[len(prefix) + len('resblocks.'):].split('.')[0]) < self.layers}
         self.transformer.load_state_dict(own)
 
     def forward(self, x, **kwargs):

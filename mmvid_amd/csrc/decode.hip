@@ -423,12 +423,19 @@ struct Gemv16Args {
 // RB: 16-row blocks per launch (1, 2, 4: up to 64 rows -- the weights are streamed ONCE for all of them; a wave runs RB MFMA chains
 // against the same weight fragments).  HALF keeps RB = 1 and covers more rows through grid.y.
 // HR (HALF only): input rows per block, 8 or 16 -- more than 16 rows in all: a block keeps its 8 staged weight rows for 16 input rows.
-template <int S, bool DIRECT, bool HALF = false, int RB = 1, int HR = 8>
+// KP (HALF only): passes over K.  K = 256 S KP; a pass stages K / KP columns of the 8 + HR rows and runs S MFMA steps per wave into the
+// same accumulator, the next pass's rows are requested before the MFMAs of this one.  K = 4,096 (c_proj of the 1,024-wide tower) in one
+// pass would be 24 rows x 8 KiB = 200 KiB of LDS, a CU has 160; two passes of 2,048 are 104 KiB and read every byte once all the same.
+// The LayerNorm path at S = 4 with four row blocks (K = 1,024, 33..64 rows) stages 64 x 2,064 B = 129 KiB; with the 32 KiB of partial
+// tiles in front that is 161 KiB, so there the partial tiles take the place of the staged rows once these are in registers (ALIAS).
+template <int S, bool DIRECT, bool HALF = false, int RB = 1, int HR = 8, int KP = 1>
 __global__ __launch_bounds__(512) void gemv16_mfma_kernel(Gemv16Args a) {
     static_assert(!HALF || RB == 1, "the 8-feature tile covers rows through grid.y");
+    static_assert(HALF || KP == 1, "only the 8-feature tile walks K in passes");
+    constexpr bool ALIAS = !DIRECT && !HALF && S * RB >= 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem16[];
     float* red = reinterpret_cast<float*>(smem16);                       // [8 waves][16 RB rows][16 features]
-    bf16_t* xs = reinterpret_cast<bf16_t*>(smem16 + 8 * RB * 256 * 4);   // [16 RB][K + 8] (LayerNorm path); HALF: 8 input + 8 weight rows
+    bf16_t* xs = reinterpret_cast<bf16_t*>(smem16 + (ALIAS ? 0 : 8 * RB * 256 * 4));   // [16 RB][K + 8] (LayerNorm path); HALF: 8 input + 8 weight rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int FT = HALF ? 8 : 16;                 // features per block
     const int K = a.K, NB = a.NB, n0 = blockIdx.x * FT, rb0 = HALF ? blockIdx.y * HR : 0;
@@ -459,7 +466,66 @@ __global__ __launch_bounds__(512) void gemv16_mfma_kernel(Gemv16Args a) {
     }
     const int epos = a.kv_cache ? (a.pos_dev ? *a.pos_dev : a.pos0) : 0;
     bf16x8_t af[RB][S];
-    if constexpr (HALF) {
+    f32x4 accp = {0.f, 0.f, 0.f, 0.f};  // (KP > 1: the accumulator of every pass)
+    if constexpr (HALF && KP > 1) {
+        static_assert(DIRECT, "the 8 x 8 tile takes bf16 rows");
+        const int kp = K / KP, ldsk = kp + 8, cpr = kp >> 3;  // columns per pass; 16-byte chunks per row and pass
+        bf16_t* wsm = xs + HR * ldsk;
+        constexpr int NCH = S / 2;  // chunks per thread for 8 rows of a pass: 8 x 256 S / 8 / 512
+        constexpr int XM = HR / 8;
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 wv[NCH], xv[NCH * XM];
+        // step f requests pass f's rows and multiplies pass f - 1: the requests are in flight under the MFMAs
+#pragma unroll
+        for (int f = 0; f <= KP; ++f) {
+            if (f > 0) {
+                if (f > 1) __syncthreads();  // (every wave has its fragments of the pass before in registers)
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    const int c = tid + 512 * i, row = c / cpr, col = (c - row * cpr) * 8;
+                    *reinterpret_cast<u32x4*>(wsm + row * ldsk + col) = wv[i];
+#pragma unroll
+                    for (int m = 0; m < XM; ++m) {
+                        const int cx = tid + 512 * (i * XM + m), rx = cx / cpr, colx = (cx - rx * cpr) * 8;
+                        *reinterpret_cast<u32x4*>(xs + rx * ldsk + colx) = xv[i * XM + m];
+                    }
+                }
+                __syncthreads();
+            }
+            if (f < KP) {
+                const int k0 = f * kp;
+#pragma unroll
+                for (int i = 0; i < NCH; ++i) {
+                    const int c = tid + 512 * i, row = c / cpr, col = (c - row * cpr) * 8;
+                    wv[i] = *reinterpret_cast<const u32x4*>(a.W + (long)(n0 + row) * K + k0 + col);
+#pragma unroll
+                    for (int m = 0; m < XM; ++m) {
+                        const int cx = tid + 512 * (i * XM + m), rx = cx / cpr, colx = (cx - rx * cpr) * 8;
+                        u32x4 v = {0u, 0u, 0u, 0u};
+                        if (rb0 + rx < NB) {
+                            if (a.xb) {
+                                v = *reinterpret_cast<const u32x4*>(a.xb + (long)(rb0 + rx) * a.ldx + k0 + colx);
+                            } else {  // fp32 rows (mmvid_gemv_rows; the tower step hands bf16 rows over): rounded here, as the staged rows of the other forms are
+                                const float* xp = a.x + (long)(rb0 + rx) * a.ldx + k0 + colx;
+                                const float4 lo = *reinterpret_cast<const float4*>(xp), hi = *reinterpret_cast<const float4*>(xp + 4);
+                                v = u32x4{pack_bf2(lo.x, lo.y), pack_bf2(lo.z, lo.w), pack_bf2(hi.x, hi.y), pack_bf2(hi.z, hi.w)};
+                            }
+                        }
+                        xv[i * XM + m] = v;
+                    }
+                }
+            }
+            if (f > 0) {
+#pragma unroll
+                for (int s = 0; s < S; ++s) {
+                    wf[s] = *reinterpret_cast<const bf16x8_t*>(wsm + rf * ldsk + kw + s * 32);
+                    af[0][s] = *reinterpret_cast<const bf16x8_t*>(xs + ra * ldsk + kw + s * 32);
+                }
+#pragma unroll
+                for (int s = 0; s < S; ++s) accp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][s], wf[s], accp, 0, 0, 0);
+            }
+        }
+    } else if constexpr (HALF) {
         // 8 weight rows + 8 input rows of K bf16 each, fetched as whole rows (a wave instruction = 1 KiB contiguous), parked in LDS at a
         // padded pitch, read back as MFMA fragments
         static_assert(DIRECT, "the 8 x 8 tile takes bf16 rows");
@@ -565,13 +631,16 @@ __global__ __launch_bounds__(512) void gemv16_mfma_kernel(Gemv16Args a) {
         for (int rbk = 0; rbk < RB; ++rbk)
 #pragma unroll
             for (int s = 0; s < S; ++s) af[rbk][s] = *reinterpret_cast<const bf16x8_t*>(xs + (long)(rbk * 16 + r16) * ldsk + kw + s * 32);
+        if constexpr (ALIAS) __syncthreads();  // (the partial tiles below overwrite the staged rows)
     }
     // ---- 3. S MFMAs per row block: C[row = 16 rbk + 4 g + i][feature = r16] over this wave's K slice
 #pragma unroll
     for (int rbk = 0; rbk < RB; ++rbk) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc = accp;
+        if constexpr (KP == 1) {
 #pragma unroll
-        for (int s = 0; s < S; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[rbk][s], wf[s], acc, 0, 0, 0);
+            for (int s = 0; s < S; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[rbk][s], wf[s], acc, 0, 0, 0);
+        }
         mfma_settle(acc);
 #pragma unroll
         for (int i = 0; i < 4; ++i) red[wave * (RB * 256) + (rbk * 16 + g * 4 + i) * 16 + r16] = acc[i];
@@ -603,16 +672,17 @@ constexpr int GV16_MIN_ROWS = 3;
 constexpr int GV16_MAXB = 64;  // rows per launch: four 16-row blocks
 bool gemv16_supported(int NB, int N, int K) {
     const int S = K / 256;
-    return NB >= 1 && NB <= GV16_MAXB && N % 16 == 0 && K % 256 == 0 && (S == 2 || S == 3 || ((S == 8 || S == 12) && N <= 1024));
+    return NB >= 1 && NB <= GV16_MAXB && N % 16 == 0 && K % 256 == 0 && (S == 2 || S == 3 || S == 4 || ((S == 8 || S == 12 || S == 16) && N <= 1024));
 }
 
 int gemv16_launch(const Gemv16Args& a, hipStream_t s) {
-    if (!gemv16_supported(a.NB, a.N, a.K) || a.ldx % 8 != 0 || (!a.x && !a.xb) || (!a.xb && a.K > 1024)) {  // (fp32 rows: K <= 1024)
-        mmvid_set_error("decode gemv (MFMA form): NB=%d (<= %d), N=%d (multiple of 16), K=%d (512 / 768 / 2048 / 3072), ldx %% 8 == 0", a.NB, GV16_MAXB, a.N, a.K);
+    const bool rows32 = !a.xb && a.K == 4096 && !a.ln_w;  // (the two-pass 8 x 8 tile also rounds plain fp32 rows while it stages them)
+    if (!gemv16_supported(a.NB, a.N, a.K) || a.ldx % 8 != 0 || (!a.x && !a.xb) || (!a.xb && a.K > 1024 && !rows32)) {  // (fp32 rows: K <= 1024, or 4096 without LayerNorm)
+        mmvid_set_error("decode gemv (MFMA form): NB=%d (<= %d), N=%d (multiple of 16), K=%d (512 / 768 / 1024, or 2048 / 3072 / 4096 with N <= 1024), ldx %% 8 == 0", a.NB, GV16_MAXB, a.N, a.K);
         return MMVID_ERR_ARG;
     }
     const bool direct = a.xb != nullptr;
-    const bool half = direct && a.N <= 1024 && a.K >= 2048;  // (narrow and long: see HALF)
+    const bool half = (direct || rows32) && a.N <= 1024 && a.K >= 2048;  // (narrow and long: see HALF)
     if (!half && a.K > 1024) {
         mmvid_set_error("decode gemv (MFMA form): K=%d > 1024 needs N <= 1024 (the 8 x 8 tile)", a.K);
         return MMVID_ERR_ARG;
@@ -620,7 +690,10 @@ int gemv16_launch(const Gemv16Args& a, hipStream_t s) {
     const int rb = half ? 1 : (a.NB <= 16 ? 1 : (a.NB <= 32 ? 2 : 4));
     const int hr = a.NB > 16 ? 16 : 8;  // (HALF: input rows per block)
     const dim3 grid(half ? a.N / 8 : a.N / 16, half ? cdiv(a.NB, hr) : 1);
-    const size_t lds = half ? 8 * 256 * 4 + (size_t)(8 + hr) * (a.K + 8) * 2 : (size_t)8 * rb * 256 * 4 + (direct ? 0 : (size_t)16 * rb * (a.K + 8) * 2);
+    const int kp = a.K > 3072 ? 2 : 1;  // (HALF: passes over K, see KP)
+    const bool alias = !direct && !half && (a.K / 256) * rb >= 16;  // (see ALIAS: the partial tiles share the staged rows' LDS)
+    const size_t lds = half ? 8 * 256 * 4 + (size_t)(8 + hr) * (a.K / kp + 8) * 2
+                            : (alias ? 0 : (size_t)8 * rb * 256 * 4) + (direct ? 0 : (size_t)16 * rb * (a.K + 8) * 2);
     auto go = [&](auto kern) {
         static bool attr = false;  // (per instantiation)
         if (!attr) {
@@ -641,11 +714,14 @@ int gemv16_launch(const Gemv16Args& a, hipStream_t s) {
     };
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
+    using I4 = std::integral_constant<int, 4>;
     using T1 = std::integral_constant<int, 1>;
     using T0 = std::integral_constant<int, 0>;
     switch (a.K / 256) {
         case 2: direct ? full(I2{}, T1{}) : full(I2{}, T0{}); break;
         case 3: direct ? full(I3{}, T1{}) : full(I3{}, T0{}); break;
+        case 4: direct ? full(I4{}, T1{}) : full(I4{}, T0{}); break;
+        case 16: hr == 16 ? go(gemv16_mfma_kernel<8, true, true, 1, 16, 2>) : go(gemv16_mfma_kernel<8, true, true, 1, 8, 2>); break;
         case 8: hr == 16 ? go(gemv16_mfma_kernel<8, true, true, 1, 16>) : go(gemv16_mfma_kernel<8, true, true>); break;
         default: hr == 16 ? go(gemv16_mfma_kernel<12, true, true, 1, 16>) : go(gemv16_mfma_kernel<12, true, true>); break;
     }
@@ -828,9 +904,9 @@ __global__ __launch_bounds__(256) void dec_embed_groups_kernel(const long long* 
 
 int gemv_launch(GemvArgs a, hipStream_t s) {
     const bool wide = a.NB > 8;  // 9-16 rows: bf16-exact staged rows only (96 KiB of LDS at 16 x 3,072)
-    if (a.NB > GV_MAXB || a.K % 8 != 0 || (long)a.NB * a.K * (a.round_in ? 2 : 4) > 24576 * 4 || (wide && !a.round_in) || a.K > 3072 ||
+    if (a.NB > GV_MAXB || a.K % 8 != 0 || (long)a.NB * a.K * (a.round_in ? 2 : 4) > 24576 * 4 || (wide && (!a.round_in || a.K > 3072)) || a.K > 4096 ||
         a.ldx % 4 != 0) {
-        mmvid_set_error("decode gemv: NB=%d (<= %d; > 8 needs round_in), K=%d (multiple of 8, <= 3072, staged rows <= 96 KiB), ldx %% 4 == 0", a.NB,
+        mmvid_set_error("decode gemv: NB=%d (<= %d; > 8 needs round_in and K <= 3072), K=%d (multiple of 8, <= 4096, staged rows <= 96 KiB), ldx %% 4 == 0", a.NB,
                         GV_MAXB, a.K);
         return MMVID_ERR_ARG;
     }
@@ -845,6 +921,10 @@ int gemv_launch(GemvArgs a, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<6, false, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);
         (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<6, true, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);
         (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<6, true, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);
+        (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<8, false, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);  // (K = 4,096: six fp32 rows)
+        (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<8, false, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);
+        (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<8, true, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);
+        (void)hipFuncSetAttribute((const void*)(gemv_rows_kernel<8, true, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 24576 * 4);
         attr = true;
     }
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, g_decode_trace); };
@@ -884,8 +964,10 @@ int gemv_launch(GemvArgs a, hipStream_t s) {
         pick(std::integral_constant<int, 2>{});
     else if (kit <= 4)
         pick(std::integral_constant<int, 4>{});
-    else
+    else if (kit <= 6)
         pick(std::integral_constant<int, 6>{});
+    else
+        pick(std::integral_constant<int, 8>{});  // K = 4,096: c_proj of the 1,024-wide tower
     return MMVID_OK;
 }
 
@@ -904,7 +986,8 @@ extern "C" int mmvid_gemv_rows(const float* x, int64_t ldx, int NB, int K, const
     a.x = x, a.ldx = ldx, a.ln_w = ln_w, a.ln_b = ln_b, a.eps = eps, a.W = (const bf16_t*)W, a.bias = bias;
     a.residual = residual, a.ldr = ldr, a.out = out, a.ldo = ldo, a.NB = NB, a.N = N, a.K = K, a.act = act;
     a.round_in = round_in, a.round_out = round_out;
-    if (round_in && NB >= GV16_MIN_ROWS && K <= 1024 && ldx % 8 == 0 && gemv16_supported(NB, N, K)) {  // 3..64 bf16-exact rows: the matrix-pipe form
+    // 3..64 bf16-exact rows: the matrix-pipe form (K = 4,096: the narrow, LayerNorm-free layer only -- c_proj of the 1,024-wide tower)
+    if (round_in && NB >= GV16_MIN_ROWS && (K <= 1024 || (K == 4096 && !ln_w)) && ldx % 8 == 0 && gemv16_supported(NB, N, K)) {
         Gemv16Args g = {};
         g.x = x, g.ldx = ldx, g.ln_w = ln_w, g.ln_b = ln_b, g.eps = eps, g.W = (const bf16_t*)W, g.bias = bias, g.residual = residual, g.ldr = ldr;
         g.out = out, g.ldo = ldo, g.NB = NB, g.N = N, g.K = K, g.act = act, g.round_out = round_out;
@@ -986,7 +1069,7 @@ extern "C" int mmvid_tower_decode_fused_slice(const mmvid_tower_cfg_t* cfg, cons
     // 3..64 sequences: the linear layers on the matrix pipe (gemv16_mfma_kernel: the weights are streamed once for all of them); 1-2: the
     // vector-ALU form (what the persistent step falls back to)
     const bool mfma = B >= GV16_MIN_ROWS && gemv16_supported(B, 3 * E, E) && gemv16_supported(B, E, F) && gemv16_supported(B, F, E);
-    MMVID_REQUIRE(mfma || B <= GV_MAXB, "tower_decode_fused: batch %d > %d needs the matrix-pipe form (widths 512 / 768, F = 4 E)", B, GV_MAXB);
+    MMVID_REQUIRE(mfma || B <= GV_MAXB, "tower_decode_fused: batch %d > %d needs the matrix-pipe form (widths 512 / 768 / 1024, F = 4 E)", B, GV_MAXB);
     bf16_t* o_bf = (bf16_t*)o;      // (MFMA form: the attention output and the activation travel as bf16 -- the operand the next layer
     bf16_t* act_bf = (bf16_t*)act;  //  would round them to anyway)
     for (int i = 0; i < cfg->layers; ++i) {

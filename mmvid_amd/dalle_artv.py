@@ -15,7 +15,7 @@ from torch import nn
 
 from . import artv_sampling, ops, sampling, token_draw
 from .artv_sampling import k_keep, keep_top
-from .clip_tower import OpenAICLIPTransformer
+from .clip_tower import OpenAICLIPTransformer, check_tower_width
 from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
 from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import AssembleSequence, LNLinear, LNLinearCrossEntropy
@@ -73,9 +73,16 @@ class DALLE(nn.Module):
         self.which_transformer = which_transformer
         if not which_transformer.startswith('openai_clip'):
             raise NotImplementedError
+        # the tower's shape: the checkpoint's where one is given, else transformer_width (heads = width / 64), else the ViT-B/32 table;
+        # in the first two cases `dim` must be that width
+        tower_width = kwargs.get('transformer_width')
+        if tower_width is not None:
+            check_tower_width(int(tower_width), 'transformer_width')
         self.transformer = OpenAICLIPTransformer(self.total_seq_len, which_transformer,
                                                  model_path=kwargs.get('openai_clip_path'),
-                                                 layers=kwargs.get('transformer_layers'))
+                                                 layers=kwargs.get('transformer_layers'),
+                                                 width=None if tower_width is None else int(tower_width),
+                                                 heads=None if tower_width is None else int(tower_width) // 64, model_dim=dim)
         self.stable = stable
         if stable:
             self.norm_by_max = DivideMax(dim=-1)

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops, sampling
-from .clip_tower import OpenAICLIPTransformer
+from .clip_tower import OpenAICLIPTransformer, check_tower_width
 from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import PosTable, AssembleSequence, BertHeads, LNLinear, Linear, LayerNormRows
 from .modules import AxialPositionalEmbedding, AxialPositionalEmbeddingList
@@ -138,11 +138,18 @@ class BERT(nn.Module):
         assert which_transformer != 'default'
         if not which_transformer.startswith('openai_clip'):
             raise NotImplementedError  # dalle_bert.py:406-407
+        # the tower's shape: the checkpoint's where one is given (clip_model.py:535-543), else transformer_width (a randomly initialised
+        # tower, heads = width / 64), else the ViT-B/32 table; in the first two cases `dim` must be that width
+        tower_width = kwargs.get('transformer_width')
+        if tower_width is not None:
+            check_tower_width(int(tower_width), 'transformer_width')
         self.transformer = OpenAICLIPTransformer(self.total_seq_len, which_transformer,
                                                  model_path=kwargs.get('openai_clip_path'), causal=True,
                                                  mask_type='mask_prev',
                                                  mask_kwargs={'index': [self.st1_tok_index, self.vid_tok_index]},
-                                                 layers=kwargs.get('transformer_layers'))
+                                                 layers=kwargs.get('transformer_layers'),
+                                                 width=None if tower_width is None else int(tower_width),
+                                                 heads=None if tower_width is None else int(tower_width) // 64, model_dim=dim)
         self.stable = stable
         if stable:
             self.norm_by_max = DivideMax(dim=-1)

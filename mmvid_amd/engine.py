@@ -47,6 +47,19 @@ class WarmupLR:
         return self.min_lr + (self.max_lr - self.min_lr) * gamma
 
 
+PROVEN_TOWER_WIDTH = 768  # the widest tower whose captured / deterministic trainer step is covered by passing tests
+
+
+def refuse_unproven_width(model, what):
+    """A captured (GraphedStep) or deterministic-mode trainer step on a tower wider than 768 is refused: the one run of that
+    combination (BERT(dim=1024), two captured deterministic-mode runs) ended in a GPU memory-access fault whose cause is not known.
+    The training forward and backward, sampling and decoding at width 1024 are tested and stay available."""
+    width = getattr(getattr(model, 'transformer', None), 'width', 0)
+    if width > PROVEN_TOWER_WIDTH:
+        raise NotImplementedError(f'{what} on a tower {width} wide: refused above width {PROVEN_TOWER_WIDTH} (this combination ended in a GPU '
+                                  'memory-access fault at width 1024 and its cause is not known)')
+
+
 class FlatTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  process_group=None, bucket_mb=64, order=None, lr_schedule=None, force_exchange=False, sparse_tables=True,
@@ -467,6 +480,8 @@ class FlatTrainer:
 
     def step(self):
         """clip_grad_norm_(max_norm) + Adam (train.py:324-325) on the averaged gradients."""
+        if _lib.is_deterministic():
+            refuse_unproven_width(self.model, 'a deterministic-mode trainer step')
         self._check_bindings()
         self.allreduce_grads()
         if self._lazy is not None:
@@ -521,6 +536,7 @@ class GraphedStep:
     """
 
     def __init__(self, trainer, fn, example_inputs, warmup=2):
+        refuse_unproven_width(trainer.model, 'a captured trainer step (GraphedStep)')
         self.trainer, self.fn = trainer, fn
         self.static = {k: v.clone() for k, v in example_inputs.items()}
         self.graph, self.capture_error = None, None

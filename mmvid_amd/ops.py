@@ -806,7 +806,8 @@ def gemv_rows(x, W, bias=None, ln=None, act=0, residual=None, round_in=False, ro
     if out is None:
         out = torch.empty(NB, N, device=x.device, dtype=f32)
     lw, lb, eps = (ln[0], ln[1], ln[2]) if ln is not None else (None, None, 0.0)
-    step = 64 if (round_in and K <= 1024 and K % 256 == 0 and N % 16 == 0) else (16 if round_in else 8)  # rows per launch: 64 bf16-exact rows on the MFMA form, 16 / 8 on the vector-ALU kernel; larger batches in slices
+    mfma = round_in and K % 256 == 0 and N % 16 == 0 and (K <= 1024 or (K == 4096 and N <= 1024 and ln is None))
+    step = 64 if mfma else (16 if round_in and K <= 3072 else 8 if (round_in or K <= 3072) else 4)  # rows per launch: 64 bf16-exact rows on the MFMA form, 16 / 8 on the vector-ALU kernel (K = 4,096: 8 bf16-staged rows = 64 KiB, 4 fp32 rows); larger batches in slices
     for r0 in range(0, NB, step):
         nb = min(step, NB - r0)
         res = residual[r0:r0 + nb] if residual is not None else None

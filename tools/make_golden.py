@@ -9,7 +9,7 @@ layout), and the reference's outputs.  Run:
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [case ...]
 
 Cases: vq vqgan_tiny vqgan_full vqgan_full16 vqgan_full16_refinit tower tower12 bert_tiny bert_tiny_visual bert_negvc bert_negvc_visual bert_flm bert_flm_bottleneck artv_tiny mask_predict
-       frontend mask_predict_race clip_vit2 clip_vit12 clip_p14_tiny clip_vitl14_2 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd long_video
+       frontend mask_predict_race clip_vit2 clip_vit12 clip_p14_tiny clip_vitl14_2 roberta_tokenizer roberta_tiny roberta_large24 fvd_prd long_video wide_models
 """
 import json
 import os
@@ -88,6 +88,13 @@ def build_vae(tiny, seed):
 def clip_state(layers):
     from mmvid_pytorch.transformers import clip_model
     clip = clip_model.CLIP(512, 224, layers, 768, 32, 77, 49408, 512, 8, layers)
+    return clip.state_dict()
+
+
+def clip_state_vitl14(layers):
+    """The ViT-L/14 layout (visual tower 1024 wide, text tower 768 wide), `layers` deep in both towers."""
+    from mmvid_pytorch.transformers import clip_model
+    clip = clip_model.CLIP(768, 224, layers, 1024, 14, 77, 49408, 768, 12, layers)
     return clip.state_dict()
 
 
@@ -237,12 +244,12 @@ def case_tower12():
     save('tower12', meta=dict(seed=23, layers=12, width=768, heads=12, L=L), manifest=man, **res)
 
 
-def _build_bert(num_visuals, use_cvae, seed, text_seq_len=16, num_targets=2, **extra):
+def _build_bert(num_visuals, use_cvae, seed, text_seq_len=16, num_targets=2, dim=768, **extra):
     from mmvid_pytorch.dalle_bert import BERT
-    ref_stubs.CLIP_STATE['sd'] = clip_state(2)
+    ref_stubs.CLIP_STATE['sd'] = clip_state(2) if dim == 768 else clip_state_vitl14(2)
     vae, _ = build_vae(True, 11)
     cvae = build_vae(True, 12)[0] if use_cvae else None
-    m = BERT(dim=768, vae=vae, cvae=cvae, num_text_tokens=49408, text_seq_len=text_seq_len,
+    m = BERT(dim=dim, vae=vae, cvae=cvae, num_text_tokens=49408, text_seq_len=text_seq_len,
              which_transformer='openai_clip_visual', num_visuals=num_visuals, num_targets=num_targets,
              openai_clip_path='x', **extra)
     man = manifest_of(m)
@@ -511,6 +518,86 @@ def case_bert_tiny():
 
 def case_bert_tiny_visual():
     _bert_case('bert_tiny_visual', 1, True)
+
+
+def case_wide_models():
+    """BERT and DALLE on the visual tower of a ViT-L/14 archive (dim 1024, 16 heads; two layers, tiny VAE of config 1): the
+    reference's state_dict manifests, and one BERT training step (the decisions it drew are stored, so a test injects them)."""
+    import mmvid_pytorch.dalle_bert as db
+    from mmvid_pytorch.dalle_artv import DALLE
+    D = 1024
+    m, man = _build_bert(0, False, 17, dim=D)
+    assert m.transformer.transformer.width == D and m.transformer.transformer.resblocks[0].attn.num_heads == 16
+    B, T, S, TL = 2, 2, 64, 16
+    text = synth_tokens('text', (B, TL), 49408, 17, low=1)
+    text[0, 11:] = 0
+    text[1, 5:] = 0
+    frames = synth_input('frames', (B, T, 3, S, S), 17, 'uniform')
+    cap = {'emb_in': [], 'tf_out': [], 'warp': []}
+    h1 = m.image_emb.register_forward_hook(lambda mod, i, o: cap['emb_in'].append(i[0].clone()))
+    h2 = m.transformer.register_forward_hook(lambda mod, i, o: cap['tf_out'].append(o.detach().clone()))
+    warp_orig = db.warp
+
+    def warp_cap(x, p):
+        y = warp_orig(x, p)
+        cap['warp'].append(y.clone())
+        return y
+
+    db.warp = warp_cap
+    m.train()
+    with torch.no_grad():
+        ctrl = m(text, visual=None, return_loss=False)
+    seed_all(123)
+    loss_msm, loss_rel, loss_vid = m(text, visual=None, target=frames, return_loss=True, rel=True, vid=True,
+                                     msm_strategy_prob=np.array([0.7, 0.1, 0.1, 0.1]),
+                                     msm_bernoulli_prob=[0.2, 0.5], rel_no_fully_masked=True,
+                                     vid_strategy_prob=np.array([0.25, 0.25, 0.25, 0.25]))
+    (7 * loss_msm + 0.5 * loss_rel + 0.5 * loss_vid).backward()
+    db.warp = warp_orig
+    h1.remove(), h2.remove()
+    with torch.no_grad():
+        target_tok = m.get_image_tokens(frames)
+        warp_tok = m.get_image_tokens(cap['warp'][0])
+        logits_msm = m.to_logits(cap['tf_out'][0][:, ctrl.shape[1]:])
+    mask1 = cap['emb_in'][0] != m.image_token_lut['[MASK]']
+    g = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    blk = 'transformer.transformer.resblocks.'
+    res = dict(text=text, frames=frames, control_emb=ctrl[:, ::2], target_tok=target_tok, warp_tok=warp_tok, mask1=mask1,
+               warped_frames=cap['warp'][0], logits_msm=logits_msm[:, ::2], losses=torch.stack([loss_msm, loss_rel, loss_vid]).detach(),
+               g_image_emb=g['image_emb.weight'][::3, ::5], g_to_logits_w=g['to_logits.1.weight'][::4, ::6],
+               g_special_emb=g['special_emb.weight'], g_text_pos=g['text_pos_emb.weight'][:, ::5],
+               g_tpos0=g['target_pos_emb.weights_0'].reshape(-1, D), g_ln1w=g[blk + '0.ln_1.weight'], g_fcb=g[blk + '1.mlp.c_fc.bias'],
+               g_inw_s=g[blk + '0.attn.in_proj_weight'][::61, ::29], g_pjw_s=g[blk + '1.mlp.c_proj.weight'][::61, ::29],
+               g_relw=g['to_logits_rel.1.weight'], g_vidw=g['to_logits_vid.1.weight'],
+               g_text_emb_rows=g['text_emb.weight'][text.view(-1).unique()][:, ::11], g_text_emb_row_ids=text.view(-1).unique(),
+               g_total_norm=torch.sqrt(sum((v.double()**2).sum() for v in g.values())).view(1))
+    ref_stubs.CLIP_STATE['sd'] = clip_state_vitl14(2)
+    vae, _ = build_vae(True, 11)
+    a = DALLE(dim=D, vae=vae, cvae=None, num_text_tokens=49408, text_seq_len=16,
+              which_transformer='openai_clip_visual', num_visuals=1, num_targets=2, openai_clip_path='x')
+    # ... and one ART-V training step (the 49,952-way head at width 1024 through the cross-entropy): loss and selected gradients
+    man_a = manifest_of(a)
+    sd_a = synth_state_dict(man_a, 19)
+    for k in list(sd_a):
+        if k.startswith('vae.'):
+            sd_a[k] = synth_tensor(k[len('vae.'):], sd_a[k].shape, 11)
+    a.load_state_dict(sd_a)
+    text_a = synth_tokens('text', (B, TL), 49408, 19, low=1)
+    text_a[0, 9:] = 0
+    frames_a = synth_input('frames', (B, T, 3, S, S), 19, 'uniform')
+    visual_a = synth_input('visual', (B, 1, 3, S, S), 19, 'uniform')
+    a.train()
+    loss_a, _, _ = a(text_a, visual=visual_a, target=frames_a, return_loss=True)
+    loss_a.backward()
+    ga = {k: p.grad for k, p in a.named_parameters() if p.grad is not None}
+    with torch.no_grad():
+        res.update(artv_text=text_a, artv_target_tok=a.get_image_tokens(frames_a), artv_visual_tok=a.get_image_tokens(visual_a.reshape(-1, 3, S, S)).view(B, -1))
+    res.update(artv_loss=loss_a.detach().view(1), artv_g_to_logits_w_s=ga['to_logits.1.weight'][::997, ::13],
+               artv_g_image_emb_s=ga['image_emb.weight'][::3, ::5], artv_g_inw_s=ga[blk + '0.attn.in_proj_weight'][::61, ::29],
+               artv_g_pjw_s=ga[blk + '1.mlp.c_proj.weight'][::61, ::29],
+               artv_g_total_norm=torch.sqrt(sum((v.double()**2).sum() for v in ga.values())).view(1))
+    save('wide_models', meta=dict(dim=D, heads=16, layers=2, seed=17, artv_seed=19, vae_seed=11, B=B, T=T, image_size=S, text_seq_len=TL, py_seed=123),
+         manifest=man, manifest_artv=man_a, **res)
 
 
 def case_artv_tiny():
@@ -1113,7 +1200,7 @@ CASES = dict(vq=case_vq, vqgan_tiny=case_vqgan_tiny, vqgan_full=case_vqgan_full,
              mask_predict=case_mask_predict, frontend=case_frontend, mask_predict_race=case_mask_predict_race,
              clip_vit2=case_clip_vit2, clip_vit12=case_clip_vit12, clip_p14_tiny=case_clip_p14_tiny,
              clip_vitl14_2=case_clip_vitl14_2, roberta_tokenizer=case_roberta_tokenizer, roberta_tiny=case_roberta_tiny,
-             roberta_large24=case_roberta_large24, fvd_prd=case_fvd_prd, long_video=case_long_video)
+             roberta_large24=case_roberta_large24, fvd_prd=case_fvd_prd, long_video=case_long_video, wide_models=case_wide_models)
 
 if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
