@@ -1,0 +1,48 @@
+/* mmvid_hip_ext.h -- entry points of libmmvid_hip.so added after the list of mmvid_hip.h was pinned.
+ *
+ * tests/test_cdecl_host.py pins mmvid_hip.h to an exact count of functions and structs, and the binding tests require the ctypes
+ * tables derived from it to equal that list.  A new entry point therefore goes HERE: same library, same plain C conventions (device
+ * pointers + sizes, caller-allocated outputs, `stream` a hipStream_t, 0 on success, message via mmvid_last_error()), read by the same
+ * strict reader (mmvid_amd/_cdecl.py) and bound by mmvid_amd/_lib.py from tables of its own (EXT_HEADER, EXT_SIGNATURES).  Adding an
+ * entry point here leaves MMVID_ABI_VERSION alone; changing one raises it, in mmvid_hip.h.
+ */
+#ifndef MMVID_HIP_EXT_H
+#define MMVID_HIP_EXT_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- Seeded sampling: the race variates of the samplers as a pure function of (video seed, purpose, substream, draw, index) ------
+ *
+ * The function.  Philox4x32-10 is the generator of Salmon et al., "Parallel random numbers: as easy as 1, 2, 3" (the Random123
+ * philox4x32 with 10 rounds: multipliers 0xD2511F53 on counter word 0 and 0xCD9E8D57 on counter word 2, key increments 0x9E3779B9 and
+ * 0xBB67AE85 per round; one round maps (c0, c1, c2, c3) to (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))).
+ * Variate i of the block that the 64-bit video seed s owns for (purpose, substream, draw) is made from
+ *     w = word (i & 3) of Philox4x32-10(counter = {i >> 2, purpose, substream, draw}, key = {s & 0xffffffff, s >> 32})
+ * (counter and key words in the order c0..c3, k0..k1; substream and draw enter as their low 32 bits) as
+ *     kind 0, uniform:  (float)(w >> 8) * 2^-24                       in [0, 1), a multiple of 2^-24
+ *     kind 1, Exp(1):   0 - logf((float)((w >> 8) + 1) * 2^-24)       the argument is an exact fp32 in (0, 1]: the result lies in
+ *                                                                     [0, 24 ln 2 = 16.64], is +0 at w >> 8 = 2^24 - 1, never inf / NaN
+ * (logf: the device's fp32 natural logarithm.)  Purposes: 1 = token race, 2 = token noise, 3 = keep race -- the `tok{t}`,
+ * `tok{t}_noise_u` and `keep{t}` tensors of the samplers; `draw` is t (mask-predict: the step; ART-V: the token's index in the target
+ * sequence); substream is 0 but for long videos, where it names the window (mmvid_amd/long_video.py: window_substream).
+ *
+ * The layout.  out is fp32 [draws][videos * rows_per_video][n], contiguous.  Row r of a block belongs to video v = r / rows_per_video
+ * and element (r, c) is variate i = (r % rows_per_video) * n + c of that video -- a video's rows_per_video * n variates of one draw lie
+ * contiguous, in index order, wherever the video sits in the batch.  Block k has draw number draw_first + k.  With draw_dev != NULL
+ * (an int32 on the device) draws must be 1 and the draw number is *draw_dev + draw_first, read on the device at execution: a captured
+ * per-token step needs no host input.  seeds: int64 [videos] on the device, each in [0, 2^63) by the Python layer's rule (the kernel
+ * takes all 64 bits as they are); substream: int32 [videos] on the device, or NULL for 0.
+ *
+ * Refused with an error (never a fault): NULL seeds or out; a negative size; rows_per_video * n > 2^34 (i >> 2 must fit counter word
+ * 0); purpose outside 1..3; kind outside 0..1; draws != 1 with draw_dev; without draw_dev a draw number outside [0, 2^32).  Zero
+ * rows, zero columns or zero draws: nothing is launched. */
+int mmvid_variates_fill(const int64_t* seeds, const int32_t* substream, int64_t videos, int64_t rows_per_video, int64_t n,
+                        int purpose, int kind, const int32_t* draw_dev, int64_t draw_first, int64_t draws,
+                        float* out, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -11,6 +11,8 @@ import re
 from collections import namedtuple
 
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'mmvid_hip.h')
+# entry points added after the list of mmvid_hip.h was pinned (tests/test_cdecl_host.py): same forms, same reader
+EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), 'mmvid_hip_ext.h')
 
 SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64,
            'float': ctypes.c_float, 'double': ctypes.c_double}

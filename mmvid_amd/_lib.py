@@ -1,9 +1,9 @@
 """ctypes binding of libmmvid_hip.so, derived from its C header.
 
 include/mmvid_hip.h is the one place the ABI is written down: _cdecl.py reads it at import (a few milliseconds) and every argument
-list, return type, struct layout and the ABI version below come from it.  A new entry point or struct field is added to the header
-only.  Two things the header does not say are stated here: the Python names of the structs, and which `int` results are values
-rather than error codes.
+list, return type, struct layout and the ABI version below come from it.  That header's list is pinned (tests/test_cdecl_host.py); a new
+entry point is added to include/mmvid_hip_ext.h only, which is read and bound the same way (EXT_HEADER, EXT_SIGNATURES).  Two things
+the header does not say are stated here: the Python names of the structs, and which `int` results are values rather than error codes.
 
 The product path has NO fallback: importing works anywhere (so host logic is testable on CPU), but the
 first kernel call without the library or without a GPU raises.
@@ -12,7 +12,7 @@ import ctypes
 import os
 from ctypes import c_float, c_int, c_int64, c_uint64, c_void_p
 
-from ._cdecl import HEADER_PATH, parse
+from ._cdecl import EXT_HEADER_PATH, HEADER_PATH, parse
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MMVID_LIB') or os.path.join(HERE, 'libmmvid_hip.so')  # (MMVID_LIB: another build of the same ABI, for same-box A/Bs)
@@ -38,6 +38,16 @@ globals().update({py: HEADER.structs[c] for py, c in STRUCTS.items()})
 SIGNATURES = {n: args for n, (res, args) in HEADER.functions.items() if res is c_int and n not in INT_VALUED}
 # ... and name -> (argtypes, restype) of those that return a value
 OTHER = {n: (args, res) for n, (res, args) in HEADER.functions.items() if n not in SIGNATURES}
+
+# include/mmvid_hip_ext.h: the entry points added after the list of mmvid_hip.h was pinned (tests/test_cdecl_host.py counts that header's
+# functions and the binding tests hold SIGNATURES | OTHER to it).  Same library, same reader, tables of their own; all return an
+# error code, so call() serves them as it serves SIGNATURES.
+with open(EXT_HEADER_PATH) as _f:
+    EXT_HEADER = parse(_f.read())
+if EXT_HEADER.structs or EXT_HEADER.constants or set(EXT_HEADER.functions) & set(HEADER.functions) or any(
+        res is not c_int for res, _ in EXT_HEADER.functions.values()):
+    raise ImportError(f'{EXT_HEADER_PATH} may declare only new functions that return an error code (structs and constants: {HEADER_PATH})')
+EXT_SIGNATURES = {n: args for n, (res, args) in EXT_HEADER.functions.items()}
 
 ABI_VERSION = HEADER.constants['MMVID_ABI_VERSION']  # what mmvid_abi_version() of a matching build returns
 _lib = None
@@ -78,6 +88,8 @@ def load():
             bind(name, args, I)
         for name, (args, res) in OTHER.items():
             bind(name, args, res)
+        for name, args in EXT_SIGNATURES.items():
+            bind(name, args, I)
         # An older build of the same ABI version given through MMVID_LIB (same-box A/Bs against a parent commit) lacks the entry points
         # added since: it loads, and calling one of them raises.  The package's own library must have them all.
         if missing and not os.environ.get('MMVID_LIB'):

@@ -1,7 +1,8 @@
 """The token loop of the ART-V sampler over the key/value cache (DALLE.generate_images, use_cache=True).
 
 One token = [head logits of the image block -> draw -> embedding row of the drawn token -> one decode step through the tower].  The
-position lives in the decode session (clip_tower.DecodeSession); the race variates come from torch's graph-safe device generator.
+position lives in the decode session (clip_tower.DecodeSession); the race variates come from torch's graph-safe device generator, or,
+with per-video seeds (`seeded`: a seeded.SeededRace), from csrc/variates.hip: block `tok0 + step` of each video's token-race stream.
 `sample` picks launch_loop (separate launches, [draw -> advance] per token: captured once and replayed in production; eager for injected
 variates, a `filter_thres` that filters, `stable` and up to 4 tokens) or, at batch 1-2, token_launch_loop (the whole token is ONE
 persistent launch, with a restart point from which launch_loop finishes the call when the device was shared under it).
@@ -22,6 +23,11 @@ import torch
 from . import _lib, ops, token_draw
 
 
+TOKEN_RACE = ops.VARIATE_PURPOSES['tok']
+# the pre-drawn variates of a whole loop, in floats (256 MB); above it the captured step draws per token
+E_ALL_MAX = 1 << 26
+
+
 def k_keep(filter_thres, total):
     return max(int((1 - filter_thres) * total), 1)
 
@@ -37,12 +43,12 @@ def keep_top(logits, k):
 class TokenLoop:
     """The buffers of one sampling call and the two halves of a token, draw(step) and advance()."""
 
-    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide=None, trace=None, steps=None):
+    def __init__(self, model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide=None, trace=None, steps=None, seeded=None):
         rows, dev = h.shape[0], h.device  # the tower's rows: B, or 2B under guidance (h = [conditional; unconditional])
         B = rows // 2 if guide is not None else rows
         c0, c1 = model._allowed_range(model.control_seq_len)
         self.model, self.ln, self.first_pos, self.temperature, self.race, self.trunc = model, model.to_logits[0], first_pos, temperature, race, trunc
-        self.guide, self.trace = guide, trace
+        self.guide, self.trace, self.seeded = guide, trace, seeded
         # steps: the tokens of this loop, a run of unknown frames (None: the whole target sequence); tok0: the run's first token as an
         # index in the target sequence, which names the injected variates
         self.V, self.steps, self.k_keep = c1 - c0, model.target_seq_len if steps is None else int(steps), k_keep(filter_thres, model.total_tokens)
@@ -56,10 +62,14 @@ class TokenLoop:
         self.lt = torch.empty(B, self.V, device=dev) if guide is not None and trunc is not None else None  # the guided, truncated value
         self.tok, self.E = torch.empty(B, dtype=torch.long, device=dev), torch.empty(B, self.V, device=dev)
         # production: the race variates of the whole loop in one draw (an exponential_ inside the captured step costs its launch and two
-        # generator-state fills per replay: 12 us per token); the draw of token n reads block n = position - first_pos.  Capped at 256 MB on top of
+        # generator-state fills per replay: 7 us per token at batch 72); the draw of token n reads block n = position - first_pos.  Capped at 256 MB on top of
         # the KV cache (batch 64 at 1,024 steps x 1,024 codes) and at the 1,024 rows the indexed draw kernel takes: larger calls draw per step
-        fits = race is None and trace is None and self.steps * B * self.V <= (1 << 26) and B <= 1024
-        self.E_all = torch.empty(self.steps, B, self.V, device=dev).exponential_() if fits else None
+        fits = race is None and trace is None and self.steps * B * self.V <= E_ALL_MAX and B <= 1024
+        self.E_all = torch.empty(self.steps, B, self.V, device=dev) if fits else None
+        if fits and seeded is None:
+            self.E_all.exponential_()
+        elif fits:  # seeded: the same block, ONE fill launch; the draw number of a token is its index in the target sequence
+            seeded.fill(self.E_all, TOKEN_RACE, 1, draw_first=self.tok0)
         self.guided = dict(logits_u=self.lu, scale=guide, rows_per_scale=1) if guide is not None else {}  # (built once: draw runs per token)
         self.variates = (self.E_all, dict(step_dev=self.sess.pos, step0=first_pos)) if fits else (self.E, {})
         self.hid = self.hbuf  # the hidden state the next draw reads: the prompt's last position, then the session's output buffer
@@ -81,8 +91,10 @@ class TokenLoop:
         E, at = self.variates
         if self.race is not None:
             E.copy_(self.race(f'tok{self.tok0 + step}', tuple(E.shape)))
-        elif self.E_all is None:
+        elif self.E_all is None and self.seeded is None:
             E.exponential_()
+        elif self.E_all is None:  # draw number tok0 + (pos - first_pos), the position read on the device: captured with the step
+            self.seeded.fill(E, TOKEN_RACE, 1, draw_first=self.tok0 - self.first_pos, draw_dev=self.sess.pos)
         token_draw.draw(lg, E, trunc=self.trunc, logit_div=T, want_y=False, tok_out=self.tok, record=rec, **self.guided, **at,
                         trunc_out=lg if self.guide is None else self.lt)  # unguided: the truncation is in place
         if rec is not None:
@@ -171,12 +183,13 @@ def token_launch_loop(loop):
     return launch_loop(loop, good_step + 1)
 
 
-def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None, guide=None, trace=None, steps=None):
+def sample(model, h, cache, first_pos, filter_thres, temperature, race, trunc=None, guide=None, trace=None, steps=None, seeded=None):
     """h [B, dim]: the hidden state of the prompt's last position, `cache` filled below first_pos -> the sampled tokens, target_seq_len columns [B, 1]
     (`steps` columns for a run of that many tokens that starts at first_pos: sample_given).
     guide (fp32 [B] on the device): h and the cache hold 2B sequences, conditional then unconditional.  trace (a list): one dict of clones
-    per token (logits, E, tok, x_in for every token but the last; scale when guided; logits_t and kept when truncated), eager loop."""
-    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide, trace, steps)
+    per token (logits, E, tok, x_in for every token but the last; scale when guided; logits_t and kept when truncated), eager loop.
+    seeded (a seeded.SeededRace over the B videos): the variates are a function of each video's seed; every path below stays as it is."""
+    loop = TokenLoop(model, h, cache, first_pos, filter_thres, temperature, race, trunc, guide, trace, steps, seeded)
     capture = race is None and trace is None and loop.k_keep >= loop.V and not model.stable and loop.steps > 4
     # (the one-launch token has no truncation and no second branch in it: a call with top_k / top_p or guidance takes the separate
     # launches; MMVID_DECODE_TOKEN=0: all do)
@@ -257,7 +270,7 @@ def check_given(given, B, T, n, V):
     return mask, tokens
 
 
-def sample_given(model, prompt, pattern, known, filter_thres, temperature, race, trunc=None, guide=None, trace=None):
+def sample_given(model, prompt, pattern, known, filter_thres, temperature, race, trunc=None, guide=None, trace=None, seeded=None):
     """One pass through the segments of a frame mask for rows that share it.  prompt [rows, 1 + control_seq_len]: <bos> text visual ids
     (rows = B, or 2B under guidance); pattern: the T mask values; known int64 [B, T * n], read under the mask -> tokens [B, T * n].
 
@@ -289,7 +302,7 @@ def sample_given(model, prompt, pattern, known, filter_thres, temperature, race,
             continue
         if h is None:  # the sequence starts with unknown frames: the prompt alone, as in a call without known frames
             h = tower.prefill(model._embed_rows(ids, 0), cache)[:, -1, :].contiguous()
-        toks = sample(model, h, cache, ids.shape[1], filter_thres, temperature, race, trunc, guide, trace, steps=hi - lo)
+        toks = sample(model, h, cache, ids.shape[1], filter_thres, temperature, race, trunc, guide, trace, steps=hi - lo, seeded=seeded)
         out[:, lo:hi] = torch.cat(toks, dim=-1)
         if i < len(runs) - 1:
             ids = torch.cat((ids, out[:, lo:hi].repeat(halves, 1)), 1)

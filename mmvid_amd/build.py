@@ -4,19 +4,19 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from ._cdecl import HEADER_PATH
+from ._cdecl import EXT_HEADER_PATH, HEADER_PATH
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, '_obj')
 LIB = os.path.join(HERE, 'libmmvid_hip.so')
-SOURCES = ['errors', 'graphs', 'vq', 'gemm', 'norm', 'attn', 'embed', 'optim', 'tower', 'decode', 'decode_persistent', 'conv', 'conv_strip', 'strict', 'sample', 'frontend', 'vqgan', 'probe', 'clip', 'roberta', 'i3d', 'frames']
+SOURCES = ['errors', 'graphs', 'vq', 'gemm', 'norm', 'attn', 'embed', 'optim', 'tower', 'decode', 'decode_persistent', 'conv', 'conv_strip', 'strict', 'sample', 'frontend', 'vqgan', 'probe', 'clip', 'roberta', 'i3d', 'frames', 'variates']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result']
 
 
 def _deps_mtime():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')]
-    hs.append(HEADER_PATH)
+    hs += [HEADER_PATH, EXT_HEADER_PATH]
     return max(os.path.getmtime(h) for h in hs)
 
 

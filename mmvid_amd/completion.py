@@ -12,7 +12,7 @@ region of `frames` with a constant (the reference's erase_real uses ones) rather
 """
 import torch
 
-from . import artv_sampling, ops, sampling
+from . import artv_sampling, ops, sampling, seeded
 
 SHAPES = '[b, T] (whole frames), [b, T, h, w] (token grid) or [b, T, H, W] (pixels)'
 
@@ -63,6 +63,18 @@ def _frames_to_tokens(model, frames, b):
 def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, mp_config=None, dynamic=True, erase_visual=False,
              vc_mode=None, face_mode=None, decode=True, paste=True, guidance_scale=None, guidance_drop=('text', 'visual'),
              negative_text=None, top_k=None, top_p=None, _race=None, _trace=None):
+    """`complete_seeded` without seeds: the variates come from torch's device generator (or from `_race`).  Its signature is pinned by
+    tests/test_artv_completion_host.py, which is why the seeded call has a name of its own."""
+    return complete_seeded(model, text, frames, given, None, visual=visual, mask_predict_steps=mask_predict_steps, mp_config=mp_config,
+                           dynamic=dynamic, erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, decode=decode, paste=paste,
+                           guidance_scale=guidance_scale, guidance_drop=guidance_drop, negative_text=negative_text, top_k=top_k,
+                           top_p=top_p, _race=_race, _trace=_trace)
+
+
+@torch.no_grad()
+def complete_seeded(model, text, frames, given, seeds, *, visual=None, mask_predict_steps=0, mp_config=None, dynamic=True,
+                    erase_visual=False, vc_mode=None, face_mode=None, decode=True, paste=True, guidance_scale=None,
+                    guidance_drop=('text', 'visual'), negative_text=None, top_k=None, top_p=None, _race=None, _trace=None):
     """Complete `b` videos of `num_targets` frames -> (frames_u8 [b, T, H, W, 3] uint8 on the device, or None without `decode`;
     tokens [b, T, n] int64).
 
@@ -70,7 +82,8 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
     marks is read as known.  Pixels are tokenised by `model.get_image_tokens` in the VQGAN's current `strict` mode; 'split' is the
     mode whose indices are exact.  `given`: see token_mask; every video may have its own.  `text`, `visual`, `erase_visual`,
     `vc_mode`, `face_mode`, `mask_predict_steps`, `mp_config`, `dynamic`, `guidance_scale`, `guidance_drop`, `negative_text`, `top_k`, `top_p`: as for
-    generate_images (guided completion: the given tokens are visible to both branches, and belong to the conditional one).
+    generate_images (guided completion: the given tokens are visible to both branches, and belong to the conditional one).  `seeds`:
+    one per video, as for BERT.mask_predict (not with erase_visual); None: the unseeded call, which is `complete`.
 
     One host read precedes the sampler's loop: the number of known tokens per video together with the count of given token ids
     outside [0, num_image_tokens), which raises ValueError.  `decode` decodes the result once, in slices of `vae._max_frames`;
@@ -78,6 +91,7 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
     with token input there are no pixels to paste and the plain byte kernel runs."""
     if mp_config is None:
         raise ValueError('complete: mp_config is required (the schedules of mask-predict, args.mp_config of the reference)')
+    seeds = seeded.check_seeds(seeds, text.shape[0], race=_race, erase_visual=erase_visual)
     drop = None
     if guidance_scale is not None or negative_text is not None:
         drop = sampling.check_guidance(model.num_visuals, model.fixed_language_model is not None, guidance_scale, guidance_drop,
@@ -111,7 +125,7 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
                 text, drop, negative_text, visual=visual, erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode))
         mask, tokens = mask.to(dev), tokens.to(dev)
         seq = model.mask_predict(control, dynamic=dynamic, steps=mask_predict_steps, mp_config=mp_config, given=(mask, tokens),
-                                 _given_unknown=unknown, _race=_race, _trace=_trace, top_k=top_k, top_p=top_p, **guide)[0]
+                                 _given_unknown=unknown, seeds=seeds, _race=_race, _trace=_trace, top_k=top_k, top_p=top_p, **guide)[0]
         out = None
         if decode:
             flat = seq.view(b * T, n)
@@ -133,7 +147,7 @@ def complete(model, text, frames, given, *, visual=None, mask_predict_steps=0, m
 @torch.no_grad()
 def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, temperature=1., erase_visual=False, vc_mode=None,
                   face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None, guidance_drop=sampling.GUIDANCE_DROPS,
-                  negative_text=None, paste=True, _race=None, _trace=None):
+                  negative_text=None, paste=True, seeds=None, _race=None, _trace=None):
     """Video prediction on the autoregressive (ART-V) model -> (frames_u8 [b, T, H, W, 3] uint8 on the device, tokens [b, T * n] int64).
 
     `frames`: as for `complete` (fp32 [b, T, 3, H, W] in [0, 1], uint8 [b, T, H, W, 3], or int64 tokens [b, T * n]); only the frames
@@ -143,12 +157,13 @@ def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, 
     do not see it -- [0, 1, 1, 0] generates frame 0 from the text and the visual control alone, then frame 3 from frames 0-2 -- so
     in-betweening key frames is the BERT's task (`complete`), and prediction from the first frames is this one's.
 
-    The other keywords are those of DALLE.generate_images, which samples (`given=(mask, tokens)`).  The result is decoded once, in
+    The other keywords (`seeds` among them) are those of DALLE.generate_images, which samples (`given=(mask, tokens)`).  The result is decoded once, in
     slices of `vae._max_frames`; with `paste` and pixel `frames` the known frames are the input's own bytes and not their VQGAN
     reconstruction (csrc/frames.hip); with token input there are no pixels to paste and the plain byte kernel runs."""
     T, n, s, f = model.num_targets, model.image_seq_len, model.image_size, model.image_fmap_size
     b, dev = text.shape[0], text.device
     mask = artv_sampling.check_frame_mask(given, b, T)  # (before the frames are tokenised)
+    seeds = seeded.check_seeds(seeds, b, race=_race, erase_visual=erase_visual)
     if isinstance(visual, (list, tuple)):  # frames [b, 3, H, W] each, as get_image_tokens takes them
         visual = torch.stack(list(visual), dim=1) if len(visual) else None
     was_training = model.training
@@ -158,7 +173,7 @@ def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, 
         _, seq = model.sample_tokens(text, visual=visual, filter_thres=filter_thres, temperature=temperature, erase_visual=erase_visual,
                                      vc_mode=vc_mode, face_mode=face_mode, use_cache=use_cache, top_k=top_k, top_p=top_p,
                                      guidance_scale=guidance_scale, guidance_drop=guidance_drop, negative_text=negative_text,
-                                     given=(mask, tokens.to(dev)), _race=_race, _trace=_trace)
+                                     given=(mask, tokens.to(dev)), seeds=seeds, _race=_race, _trace=_trace)
         flat = seq.reshape(b * T, n)
         out = torch.empty(b * T, s, s, 3, device=dev, dtype=torch.uint8)
         grid = mask.to(dev).view(b * T, 1, 1).expand(b * T, f, f).contiguous()

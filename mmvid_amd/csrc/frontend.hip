@@ -12,26 +12,11 @@
 // oracle/frontend.py.  All kernels are elementwise / tiny: HBM-bound.
 #include "../../include/mmvid_hip.h"
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
-// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3") --------------------------------
-struct U4 {
-    uint32_t x, y, z, w;
-};
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1,
-                       n3 = (uint32_t)p0;
-        c0 = n0, c1 = n1, c2 = n2, c3 = n3;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ float u01(uint32_t v) { return (float)(v >> 8) * (1.0f / 16777216.0f); }  // [0, 1)
-
+// ---- Philox4x32-10 and the word-to-uniform mapping u01: philox.h -------------------------------------------------
 struct Rng {  // one stream = (seed, step, sample, purpose); draw i of the stream = word (i & 3) of block (i >> 2)
     uint32_t k0, k1, step, sample, purpose;
     __device__ __forceinline__ float uniform(uint32_t i) const {

@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import artv_sampling, ops, sampling, token_draw
+from . import artv_sampling, ops, sampling, seeded, token_draw
 from .artv_sampling import k_keep, keep_top
 from .clip_tower import OpenAICLIPTransformer, check_tower_width
 from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
@@ -328,7 +328,7 @@ class DALLE(nn.Module):
     @eval_decorator
     def generate_images(self, text, *, clip=None, visual=None, mask=None, filter_thres=0.5, temperature=1.,
                         erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None,
-                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, given=None, _race=None, _trace=None, **kwargs):
+                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, given=None, seeds=None, _race=None, _trace=None, **kwargs):
         """dalle_artv.py:236-304.  use_cache=True (default): the prompt runs once and every sampled token costs one
         incremental step over the per-layer key/value cache; use_cache=False: the reference's algorithm (the whole
         transformer over the growing prefix per token).  Both draw from the same distribution: softmax over the image
@@ -351,11 +351,15 @@ class DALLE(nn.Module):
         front of it).  Rows with the same mask run together, one pass through artv_sampling.sample_given per distinct mask; the visual
         tokens are computed once for the whole batch.  Under guidance both branches carry the same known and drawn tokens.  Known
         positions draw nothing: `_race` is asked for `tok{j}` of the generated positions j of the target sequence only, `_trace` gets
-        records of those only, and both need one mask for the whole batch."""
+        records of those only, and both need one mask for the whole batch.
+
+        `seeds` (a sequence or integer tensor of B values in [0, 2^63), one per video; guided: still one per video): every token race
+        draws variates that are a function of the video's seed and the token's index in the target sequence (mmvid_amd/seeded.py), not of
+        torch's generator, the row or the batch; several masks in one batch are fine.  Refused with `_race` and with erase_visual."""
         return self._decode_tokens(*self.sample_tokens(text, visual=visual, filter_thres=filter_thres, temperature=temperature,
                                                        erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, use_cache=use_cache,
                                                        top_k=top_k, top_p=top_p, guidance_scale=guidance_scale, guidance_drop=guidance_drop,
-                                                       negative_text=negative_text, given=given, _race=_race, _trace=_trace), clip)
+                                                       negative_text=negative_text, given=given, seeds=seeds, _race=_race, _trace=_trace), clip)
 
     def _decode_tokens(self, text, tokens, clip=None):
         """The tail of generate_images: tokens [B, target_seq_len] -> (images, [], None), or (images, clip scores)."""
@@ -371,11 +375,13 @@ class DALLE(nn.Module):
     @eval_decorator
     def sample_tokens(self, text, *, visual=None, filter_thres=0.5, temperature=1., erase_visual=False, vc_mode=None, face_mode=None,
                       use_cache=True, top_k=None, top_p=None, guidance_scale=None, guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None,
-                      given=None, _race=None, _trace=None):
-        """The sampler of generate_images without the decode -> (text [B, text_seq_len], tokens int64 [B, target_seq_len])."""
+                      given=None, seeds=None, _race=None, _trace=None, _substream=None):
+        """The sampler of generate_images without the decode -> (text [B, text_seq_len], tokens int64 [B, target_seq_len]).
+        `_substream` (one int per video, with `seeds`): the window of a long video (long_video.window_substream)."""
         tsl = self.text_seq_len
         text = text[:, :tsl]
         B = text.shape[0]
+        seeds = seeded.check_seeds(seeds, B, race=_race, erase_visual=erase_visual)
         groups = None
         if given is not None:
             gmask, gtok = artv_sampling.check_given(given, B, self.num_targets, self.image_seq_len, self.num_image_tokens)
@@ -395,6 +401,7 @@ class DALLE(nn.Module):
         vis_tok = self._visual_tokens(visual, erase_visual, True, vc_mode, face_mode, None)
         scale = None
         text_c = text
+        race = seeded.SeededRace(seeds, text.device, _substream) if seeds is not None else None
         if guide is not None:  # rows B..2B-1: the unconditional prompt (both branches share the erase and the face region of vis_tok)
             drop, scale = guide[0], self._scale_vector(guide[1], B, text.device)
             text_u, vis_u = sampling.unconditional_inputs(text, vis_tok, drop, negative_text[:, :tsl] if negative_text is not None else None)
@@ -402,7 +409,7 @@ class DALLE(nn.Module):
                 vis_u = torch.full_like(vis_tok, -1)
             text, vis_tok = torch.cat((text, text_u), 0), (torch.cat((vis_tok, vis_u), 0) if vis_tok is not None else None)
         if groups is None:
-            return text_c, self._sample_rows(text, vis_tok, B, None, None, filter_thres, temperature, use_cache, trunc, scale, _race, _trace)
+            return text_c, self._sample_rows(text, vis_tok, B, None, None, filter_thres, temperature, use_cache, trunc, scale, _race, _trace, race)
         gtok = gtok.to(text.device)
         parts = []
         for pattern, rows in groups:
@@ -413,22 +420,26 @@ class DALLE(nn.Module):
                 sel = idx if guide is None else torch.cat((idx, idx + B))
                 t, v, g = text.index_select(0, sel), (vis_tok.index_select(0, sel) if vis_tok is not None else None), gtok.index_select(0, idx)
                 s = scale.index_select(0, idx).contiguous() if scale is not None else None
-            parts.append((rows, self._sample_rows(t, v, len(rows), pattern, g, filter_thres, temperature, use_cache, trunc, s, _race, _trace)))
+            parts.append((rows, self._sample_rows(t, v, len(rows), pattern, g, filter_thres, temperature, use_cache, trunc, s, _race, _trace,
+                                                  race if race is None or len(groups) == 1 else race.rows(rows))))
         return text_c, artv_sampling.scatter_rows(parts, B)
 
-    def _sample_rows(self, text, vis_tok, B, pattern, known, filter_thres, temperature, use_cache, trunc, scale, _race, _trace):
+    def _sample_rows(self, text, vis_tok, B, pattern, known, filter_thres, temperature, use_cache, trunc, scale, _race, _trace, seeded_race=None):
         """Tokens [B, target_seq_len] for prompts that share one frame mask `pattern` (None: nothing known).  text / vis_tok: B rows, or
-        [conditional; unconditional] = 2B rows with `scale`."""
+        [conditional; unconditional] = 2B rows with `scale`.  seeded_race: the seeded.SeededRace of these B videos."""
         rows = text.shape[0]
         cl = self.control_seq_len
         c0, c1 = self._allowed_range(cl)
         if use_cache:
             prompt = torch.cat(self._prompt_ids(text, vis_tok), 1)  # <bos> text visual: positions 0 .. cl
             if pattern is not None:
-                return artv_sampling.sample_given(self, prompt, pattern, known, filter_thres, temperature, _race, trunc, scale, _trace)
+                return artv_sampling.sample_given(self, prompt, pattern, known, filter_thres, temperature, _race, trunc, scale, _trace, seeded_race)
             cache = self.transformer.new_kv_cache(rows, self.total_seq_len, text.device)
             h = self.transformer.prefill(self._embed_rows(prompt, 0), cache)[:, -1, :].contiguous()
-            return torch.cat(artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc, scale, _trace), dim=-1)
+            return torch.cat(artv_sampling.sample(self, h, cache, prompt.shape[1], filter_thres, temperature, _race, trunc, scale, _trace,
+                                                  seeded=seeded_race), dim=-1)
+        if seeded_race is not None:  # (the uncached path asks its hook per token: the seeded hook answers to the same names)
+            _race = seeded_race
         n = self.image_seq_len
         image = torch.empty(rows, 0, dtype=torch.long, device=text.device)
         runs = artv_sampling.segments(pattern) if pattern is not None else [(False, 0, self.num_targets)]

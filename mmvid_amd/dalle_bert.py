@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import ops, sampling
+from . import ops, sampling, seeded
 from .clip_tower import OpenAICLIPTransformer, check_tower_width
 from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import PosTable, AssembleSequence, BertHeads, LNLinear, Linear, LayerNormRows
@@ -575,11 +575,14 @@ class BERT(nn.Module):
     def generate_images(self, text, *, visual=None, mask=None, img=None, argmax=False, dynamic=True, debug=False,
                         erase_visual=False, mask_predict_steps=10, preserve=None, t_overlap=1, pc_mode=None,
                         vc_mode=None, face_mode=None, mp_config=None, long_mode='long', guidance_scale=None,
-                        guidance_drop=('text', 'visual'), negative_text=None, top_k=None, top_p=None, **kwargs):
+                        guidance_drop=('text', 'visual'), negative_text=None, top_k=None, top_p=None, seeds=None, **kwargs):
         """dalle_bert.py:434-487 -> (images [b,T,3,H,W], pnag_samples, img_seq [(b T), n]).  `guidance_scale` (a float, one per step,
         one per video or [steps, b]: sampling.guidance_table) switches classifier-free guidance on; see guidance_control for
         `guidance_drop` and `negative_text`.  `top_k` / `top_p` (an int / a float, or one per step: sampling.check_truncation) draw
-        every token from the k most likely classes / from the nucleus of mass top_p (of the guided distribution when guided)."""
+        every token from the k most likely classes / from the nucleus of mass top_p (of the guided distribution when guided).  `seeds` (a
+        sequence or integer tensor of b values in [0, 2^63), one per video): see mask_predict."""
+        if seeded.check_seeds(seeds, text.shape[0], race=kwargs.get('_race'), erase_visual=erase_visual) is not None:
+            kwargs.update(seeds=seeds)
         drop = sampling.check_guidance(self.num_visuals, self.fixed_language_model is not None, guidance_scale, guidance_drop,
                                        negative_text)
         if top_k is not None or top_p is not None:
@@ -613,10 +616,18 @@ class BERT(nn.Module):
     @torch.no_grad()
     def mask_predict(self, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1,
                      mp_config=None, long_mode='long', _race=None, _trace=None, given=None, _given_unknown=None, uncond_emb=None,
-                     guidance_scale=None, top_k=None, top_p=None, **kwargs):
+                     guidance_scale=None, top_k=None, top_p=None, seeds=None, _substream=None, **kwargs):
         """dalle_bert.py:514-714, batched over videos and beam candidates on the device (mmvid_amd/sampling.py).  `given` = (mask
         [b, TS], tokens [b, TS]): per-video known tokens (mmvid_amd/completion.py).  `uncond_emb` [b, csl, E] with `guidance_scale`:
-        classifier-free guidance; `top_k`, `top_p`: truncated sampling (both: sampling.mask_predict)."""
+        classifier-free guidance; `top_k`, `top_p`: truncated sampling (both: sampling.mask_predict).
+
+        `seeds` (a sequence or integer tensor of b values in [0, 2^63), one per video): the token race, the Gumbel noise and the keep
+        race of a video draw variates that are a function of its seed, the step and the (candidate, position, class) index
+        (mmvid_amd/seeded.py) -- not of torch's generator, the video's row, the batch size or its batch mates.  Refused with `_race`.
+        `_substream` (one int per video, with `seeds`): the window of a long video (long_video.window_substream)."""
+        seeds = seeded.check_seeds(seeds, control_emb.shape[0], race=_race)
+        if seeds is not None:  # the sampler's hook, filled by csrc/variates.hip: the sampler itself does not know
+            _race = seeded.SeededRace(seeds, control_emb.device, _substream)
         return sampling.mask_predict(self, control_emb, dynamic=dynamic, debug=debug, steps=steps, preserve=preserve,
                                      t_overlap=t_overlap, mp_config=mp_config, long_mode=long_mode, race=_race, trace=_trace,
                                      given=given, given_unknown=_given_unknown, uncond_emb=uncond_emb, guidance_scale=guidance_scale,

@@ -19,7 +19,7 @@ from collections import namedtuple
 
 import torch
 
-from . import ops
+from . import ops, seeded
 
 # given: (start, stop) frames of the previous level's timeline handed to the window, None = nothing; passes / emits: (start, stop)
 # frames of the window's own T frames that go into the next level's timeline / into the output
@@ -73,6 +73,23 @@ def plan(mode, num_targets, t_repeat, t_overlap=1):
     return levels
 
 
+def window_substream(level, window):
+    """The substream of seeded sampling that belongs to window `window` of level `level` of a plan: (level << 16) | window, an int32.
+    It is the one statement of that id.  A level's sampler rows are (window, video) pairs, row = window * b + video; under `seeds` row
+    r draws from the streams of (seed of video r % b, substream of window r // b) -- a function of the plan alone, not of b, of
+    `max_rows` or of the chunk a row falls into.  Level 0, window 0 is substream 0, the substream of a call outside this module: the
+    first clip of a long video is the clip generate_images makes from the same seed."""
+    level, window = int(level), int(window)
+    if not (0 <= level < 1 << 15 and 0 <= window < 1 << 16):
+        raise ValueError(f'window_substream: level {level} / window {window} outside [0, 2^15) / [0, 2^16)')
+    return (level << 16) | window
+
+
+def row_streams(seeds, level, rows, b):
+    """(seeds, substreams) of sampler rows [rows[0], rows[1]) of a level, row = window * b + video: two host lists."""
+    return ([seeds[r % b] for r in range(rows[0], rows[1])], [window_substream(level, r // b) for r in range(rows[0], rows[1])])
+
+
 def frames_out(levels):
     """Length of the output timeline of a plan."""
     return sum(w.emits[1] - w.emits[0] for lev in levels for w in lev.windows)
@@ -118,12 +135,13 @@ def run(levels, sample, *, b, num_targets, mask_id, start=None, max_rows=None, t
 
 
 def bert_sampler(model, text, *, visual=None, mask_predict_steps=0, mp_config=None, dynamic=True, erase_visual=False, vc_mode=None,
-                 face_mode=None, seen=None, _race=None):
+                 face_mode=None, seen=None, seeds=None, _race=None):
     """The `sample` of `run` on a BERT (in eval mode, under no_grad): control rows for rows [row0, row1) of a level, then ONE
     `mask_predict` call for them.  Control rows are computed once per video and repeated when nothing random enters them
     (`erase_visual` false and `vc_mode` None); otherwise per window with one forward each, as the reference's generate_images makes
     one per window (erase_codebook_face draws once per call: every window draws its own region).  `seen` (a dict) receives per level
-    (rows whose control sequence was computed, control rows of the last chunk)."""
+    (rows whose control sequence was computed, control rows of the last chunk).  `seeds` (check_seeds' list, one per video): every row
+    draws from its video's seed and its window's substream (row_streams)."""
     b, dev = text.shape[0], text.device
     fixed_control = not erase_visual and vc_mode is None
     ctl = dict(erase_visual=erase_visual, erase_visual_half=True, vc_mode=vc_mode, face_mode=face_mode, return_loss=False)
@@ -147,8 +165,11 @@ def bert_sampler(model, text, *, visual=None, mask_predict_steps=0, mp_config=No
         if seen is not None:
             seen[level] = (seen.get(level, (0, None))[0] + computed, control)
         race = None if _race is None else (lambda name, shape: _race(f'L{level}c{chunk}/{name}', shape))
+        streams = {}
+        if seeds is not None:
+            streams['seeds'], streams['_substream'] = row_streams(seeds, level, rows, b)
         return model.mask_predict(control, dynamic=dynamic, steps=mask_predict_steps, preserve=preserve, t_overlap=overlap,
-                                  mp_config=mp_config, long_mode=long_mode, _race=race)[0]
+                                  mp_config=mp_config, long_mode=long_mode, _race=race, **streams)[0]
 
     return sample
 
@@ -157,15 +178,31 @@ def bert_sampler(model, text, *, visual=None, mask_predict_steps=0, mp_config=No
 def generate_long(model, text, *, visual=None, mode='long', t_repeat=10, t_overlap=1, real_frames=None, which_vae='vae',
                   mask_predict_steps=0, mp_config=None, dynamic=True, erase_visual=False, vc_mode=None, face_mode=None, decode=True,
                   max_rows=MAX_ROWS, trace=None, _race=None):
+    """`generate_long_seeded` without seeds: the variates come from torch's device generator (or from `_race`).  Its signature is pinned
+    by tests/test_artv_completion_host.py, which is why the seeded call has a name of its own."""
+    return generate_long_seeded(model, text, None, visual=visual, mode=mode, t_repeat=t_repeat, t_overlap=t_overlap, real_frames=real_frames,
+                                which_vae=which_vae, mask_predict_steps=mask_predict_steps, mp_config=mp_config, dynamic=dynamic,
+                                erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, decode=decode, max_rows=max_rows,
+                                trace=trace, _race=_race)
+
+
+@torch.no_grad()
+def generate_long_seeded(model, text, seeds, *, visual=None, mode='long', t_repeat=10, t_overlap=1, real_frames=None, which_vae='vae',
+                         mask_predict_steps=0, mp_config=None, dynamic=True, erase_visual=False, vc_mode=None, face_mode=None,
+                         decode=True, max_rows=MAX_ROWS, trace=None, _race=None):
     """utils_train.py:1337-1526 on a BERT -> (frames_u8 [b, F, H, W, 3] uint8 on the device, or None without `decode`;
     tokens [b, F, image_seq_len] int64).  `text`: [b, text_seq_len] ids, or [b, text_feature_dim] features with a fixed language
     model.  `real_frames` [b, T, 3, H, W] in [0, 1]: the frames mode 'interp_real' starts from.  `max_rows`: rows per sampler call
     (a level of more rows runs in consecutive chunks, in row order; None: no cap).  `_race(name, shape)` supplies the sampler's variates, names
     prefixed with 'L{level}c{chunk}/'.  `trace` (a list): per level the dict of `run` plus `control_rows`, the rows whose control
     sequence (text, visual tokens) was computed -- b per call when nothing random enters it, every row otherwise, each window then
-    drawing its own erasure as the reference does by calling forward per window -- and `control`, the control rows of its last chunk."""
+    drawing its own erasure as the reference does by calling forward per window -- and `control`, the control rows of its last chunk.
+    `seeds` (a sequence or integer tensor of b values in [0, 2^63), one per video): every window of a video draws from the video's
+    seed and the window's own substream (window_substream), whatever b and max_rows are.  Refused with `_race` and erase_visual.  None:
+    the unseeded call, which is `generate_long`."""
     if mp_config is None:
         raise ValueError('generate_long: mp_config is required (the schedules of mask-predict, args.mp_config of the reference)')
+    seeds = seeded.check_seeds(seeds, text.shape[0], race=_race, erase_visual=erase_visual)
     T, n = model.num_targets, model.image_seq_len
     levels = plan(mode, T, t_repeat, t_overlap)
     b, dev = text.shape[0], text.device
@@ -181,7 +218,7 @@ def generate_long(model, text, *, visual=None, mode='long', t_repeat=10, t_overl
             start = model.get_image_tokens(real_frames, reshape=True, which_vae=which_vae).view(b, T, n)
         seen = {} if trace is not None else None
         sample = bert_sampler(model, text, visual=visual, mask_predict_steps=mask_predict_steps, mp_config=mp_config, dynamic=dynamic,
-                              erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, seen=seen, _race=_race)
+                              erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, seen=seen, seeds=seeds, _race=_race)
         own = [] if trace is not None else None
         tokens = run(levels, sample, b=b, num_targets=T, mask_id=model.image_token_lut['[MASK]'], start=start, max_rows=max_rows,
                      trace=own)
@@ -203,11 +240,12 @@ def generate_long(model, text, *, visual=None, mode='long', t_repeat=10, t_overl
         model.train(was_training)
 
 
-def artv_sampler(model, text, *, visual=None, _race=None, **sampling_kw):
+def artv_sampler(model, text, *, visual=None, seeds=None, _race=None, **sampling_kw):
     """The `sample` of `run` on an ART-V model (dalle_artv.DALLE, in eval mode) for mode 'long': the last `t_overlap` frames of
     `preserve` (the previous clip) are the known first frames of the next clip, which enter through the prefill
     (DALLE.sample_tokens(given=...)); the first clip is a plain call.  `sampling_kw`: the sampling keywords of generate_images.  The
-    interp modes hand a window frames that lie AFTER the ones it generates, which a causal model cannot use: ValueError."""
+    interp modes hand a window frames that lie AFTER the ones it generates, which a causal model cannot use: ValueError.  `seeds`: as
+    for bert_sampler."""
     b = text.shape[0]
     T, n = model.num_targets, model.image_seq_len
 
@@ -226,21 +264,26 @@ def artv_sampler(model, text, *, visual=None, _race=None, **sampling_kw):
             tokens[:, :o * n] = preserve.reshape(rows[1] - rows[0], T, n)[:, T - o:].reshape(-1, o * n)
             given = (mask, tokens)
         race = None if _race is None else (lambda name, shape: _race(f'L{level}c{chunk}/{name}', shape))
-        return model.sample_tokens(t, visual=v, given=given, _race=race, **sampling_kw)[1]
+        streams = {}
+        if seeds is not None:
+            streams['seeds'], streams['_substream'] = row_streams(seeds, level, rows, b)
+        return model.sample_tokens(t, visual=v, given=given, _race=race, **streams, **sampling_kw)[1]
 
     return sample
 
 
 @torch.no_grad()
 def generate_long_artv(model, text, *, visual=None, mode='long', t_repeat=10, t_overlap=1, decode=True, max_rows=MAX_ROWS, trace=None,
-                       _race=None, **sampling_kw):
+                       seeds=None, _race=None, **sampling_kw):
     """Long extrapolation on an ART-V model -> (frames_u8 [b, F, H, W, 3] uint8 on the device, or None without `decode`; tokens
     [b, F, image_seq_len] int64): clip k + 1 continues the last `t_overlap` frames of clip k (plan / run of mode 'long', one window per
     level).  The interp modes raise ValueError: they need the future.  `sampling_kw`: the sampling keywords of generate_images;
-    `_race(name, shape)` supplies the variates, names prefixed with 'L{level}c{chunk}/'.  `trace` (a list): the dicts of `run`."""
+    `_race(name, shape)` supplies the variates, names prefixed with 'L{level}c{chunk}/'.  `trace` (a list): the dicts of `run`.
+    `seeds`: as for generate_long_seeded (clip k of a video draws from substream window_substream(k, 0))."""
     if mode in MODES and mode != 'long':
         raise ValueError(f'mode={mode!r}: an ART-V model extrapolates only (mode "long"); the interp modes condition a window on frames '
                          'that come after the ones it generates')
+    seeds = seeded.check_seeds(seeds, text.shape[0], race=_race, erase_visual=sampling_kw.get('erase_visual', False))
     T, n = model.num_targets, model.image_seq_len
     levels = plan(mode, T, t_repeat, t_overlap)
     b, dev = text.shape[0], text.device
@@ -249,7 +292,7 @@ def generate_long_artv(model, text, *, visual=None, mode='long', t_repeat=10, t_
     was_training = model.training
     model.eval()
     try:
-        sample = artv_sampler(model, text, visual=visual, _race=_race, **sampling_kw)
+        sample = artv_sampler(model, text, visual=visual, seeds=seeds, _race=_race, **sampling_kw)
         tokens = run(levels, sample, b=b, num_targets=T, mask_id=-1, max_rows=max_rows, trace=trace)
         frames = None
         if decode:

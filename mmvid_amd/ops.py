@@ -620,6 +620,32 @@ def exponential_like(shape, device):
     return torch.empty(shape, device=device, dtype=f32).exponential_()
 
 
+VARIATE_PURPOSES = {'tok': 1, 'noise': 2, 'keep': 3}  # token race, token noise, keep race (include/mmvid_hip_ext.h)
+
+
+def variates_fill(out, seeds, rows_per_video, purpose, kind, draw_first=0, draw_dev=None, substream=None):
+    """Seeded race variates into `out` (f32, contiguous): [R, n], or [draws, R, n] for draws draw_first .. draw_first + draws - 1 in one
+    launch, R = len(seeds) * rows_per_video rows of which rows_per_video consecutive ones belong to each video.  seeds int64 [videos],
+    substream int32 [videos] or None (0), draw_dev an int32 device scalar or None: with it `out` is one draw, number draw_dev +
+    draw_first.  purpose 1..3 (VARIATE_PURPOSES), kind 0 = uniform [0, 1), 1 = Exp(1).  The value of (video, index) is a function of
+    (seed, substream, purpose, draw, index) alone: include/mmvid_hip_ext.h.  -> out"""
+    _chk(out, f32, 'out')
+    _chk(seeds, i64, 'seeds')
+    if substream is not None:
+        _chk(substream, torch.int32, 'substream')
+        assert substream.shape == seeds.shape
+    if draw_dev is not None:
+        _chk(draw_dev, torch.int32, 'draw_dev')
+    assert seeds.dim() == 1 and out.dim() in (2, 3) and (out.dim() == 2 or draw_dev is None)
+    videos, rpv, n = seeds.shape[0], int(rows_per_video), out.shape[-1]
+    draws = out.shape[0] if out.dim() == 3 else 1
+    if out.shape[-2] != videos * rpv:
+        raise ValueError(f'variates_fill: {out.shape[-2]} rows for {videos} videos of {rpv} rows')
+    call('mmvid_variates_fill', _p(seeds), _p(substream), videos, rpv, n, int(purpose), int(kind), _p(draw_dev), int(draw_first), draws,
+         _p(out), _stream())
+    return out
+
+
 def sample_race(logits, E, noise_u=None, temperature=0.0, logit_div=1.0, tok_offset=0, want_y=True, tok_out=None, step_dev=None, step0=0):
     """logits [R, V] f32 (row stride = logits.stride(0)), E [R, V] f32 Exp(1) variates -> (tok int64 [R] (tok_out if given), y f32 [R]).
     step_dev (int32 device scalar): E is [draws, R, V] and draw number step_dev - step0 is used (token-only form: want_y False, no noise)."""
