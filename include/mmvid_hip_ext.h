@@ -42,6 +42,27 @@ int mmvid_variates_fill(const int64_t* seeds, const int32_t* substream, int64_t 
                         int purpose, int kind, const int32_t* draw_dev, int64_t draw_first, int64_t draws,
                         float* out, void* stream);
 
+/* ---- Weight EMA: an exponential moving average of the flat fp32 weights, updated on the device after the optimiser ----------------
+ *
+ * The rule (csrc/ema.hip; tests/ema_ref.py is the host replica, bit for bit).  t = *step_dev where step_dev != NULL (an fp32 on the
+ * device: the count of finished optimiser steps, this one included, read at execution so that a captured step needs no host input),
+ * else (float)step.  Then, every operation one correctly rounded fp32 operation,
+ *     d    = warmup ? fminf(decay, (1.f + t) / (10.f + t)) : decay
+ *     a    = 1.f - d
+ *     ema' = fmaf(a, p - ema, ema)             for each of the n elements; p - ema is an fp32 subtraction of its own
+ * Where ema == p the result is p, bit for bit (but for ema = p = -0, which IEEE arithmetic turns into +0: the same number).  Denormal
+ * intermediates are left unspecified.
+ *
+ * Lazy rows: row_flags, table_lo, table_rows, rowlen as in mmvid_adam_step_rows (a table of table_rows x rowlen elements at element
+ * table_lo of both buffers, one uint8 flag per row on the device; row_flags NULL: no table).  A row whose flag is 0 is neither read nor
+ * written: the caller keeps ema == p there, where the update is the identity.
+ *
+ * Refused with an error (never a fault, nothing launched): NULL ema or p; ema == p or overlapping ranges; n < 0; a pointer that is
+ * not 16-byte aligned; decay outside [0, 1) or NaN; step < 1 without step_dev; a lazy table that does not lie inside [0, n) or whose
+ * table_lo or rowlen is not a multiple of 4.  n == 0: nothing is launched. */
+int mmvid_ema_update(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
+                     const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

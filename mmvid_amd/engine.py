@@ -63,8 +63,15 @@ def refuse_unproven_width(model, what):
 class FlatTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  process_group=None, bucket_mb=64, order=None, lr_schedule=None, force_exchange=False, sparse_tables=True,
-                 lazy_rows=True, exchange=None):
+                 lazy_rows=True, exchange=None, ema_decay=None, ema_warmup=False):
         self.model = model
+        # weight EMA (INTEGRATION.md "Weight EMA"): None = off -- no buffer, no launch, state_dict() unchanged key for key
+        if ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= float(ema_decay) < 1.0:  # (NaN, inf: False)
+                raise ValueError(f'ema_decay={ema_decay!r}: a number in [0, 1), or None for no EMA')
+        elif ema_warmup:
+            raise ValueError('ema_warmup=True needs ema_decay')
+        self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
         # how a dense gradient message is summed over the ranks: 'allreduce' (one RCCL all-reduce: a ring, bound by ONE xGMI link
         # per hop) or 'direct' (every rank sends shard j of the message straight to rank j -- all_to_all over the 7
         # point-to-point links at once --, sums the shards it received in rank order, and the summed shards are all-gathered).
@@ -94,6 +101,10 @@ class FlatTrainer:
         self.M = torch.zeros(tot, device=dev, dtype=torch.float32)
         self.V = torch.zeros(tot, device=dev, dtype=torch.float32)
         self.S = torch.zeros(tot, device=dev, dtype=torch.bfloat16) if dev.type == 'cuda' else None
+        # E: the averaged weights, fp32 in the layout of P, primed (E <- P) by the first step() or the first reader; ES: their bf16
+        # shadow, allocated by the first `with ema_weights():`
+        self.E = torch.zeros(tot, device=dev, dtype=torch.float32) if self.ema_decay is not None else None
+        self.ES, self._ema_primed, self._ema_scope = None, False, False
         for p, o in zip(self.params, offs):
             n = p.numel()
             self.P[o:o + n].copy_(p.detach().reshape(-1))
@@ -179,29 +190,35 @@ class FlatTrainer:
         z['dirty'][z['dirty_n']:z['dirty_n'] + n].copy_(ids)
         z['dirty_n'] += n
 
-    def _shadow_view(self, p):
+    def _shadow_view(self, p, S=None):
         i = next(k for k, q in enumerate(self.params) if q is p)
         o = self.offsets[i]
-        return self.S[o:o + p.numel()].view(p.shape)
+        return (self.S if S is None else S)[o:o + p.numel()].view(p.shape)
 
-    def _attach_shadows(self):
+    def _attach_shadows(self, S=None):
         """Hand the model views of the flat bf16 shadow for every weight its MFMA kernels read in bf16: the tower's
         matrices and each head listed by `model.head_shadow_targets()` (BERT: to_logits; ART-V: the 51,584-way to_logits).
-        A weight that is frozen (not in the flat buffer) keeps the model's own cast-on-change copy."""
+        A weight that is frozen (not in the flat buffer) keeps the model's own cast-on-change copy.  S: the flat bf16 buffer the
+        views are taken from (default self.S; `ema_weights()` passes the shadow of the averaged weights).  The model records each
+        parameter's data_ptr with the view, so the parameters must already point where they will be read from."""
         m = self.model
         self._tower_shadow_attached = False
         tw = getattr(m, 'transformer', None)
         if tw is not None and hasattr(tw, 'attach_shadow') and all(p.requires_grad for p in tw._matrix_params()):
-            tw.attach_shadow([self._shadow_view(p) for p in tw._matrix_params()])
+            tw.attach_shadow([self._shadow_view(p, S) for p in tw._matrix_params()])
             self._tower_shadow_attached = True
+        elif tw is not None and hasattr(tw, '_shadow_key'):
+            tw._shadow_key = None  # a tower that casts for itself is keyed on (version, data_ptr): neither sees a kernel's write
         if hasattr(m, 'attach_head_shadow') and hasattr(m, 'head_shadow_targets'):
             for lin in m.head_shadow_targets():
                 if lin.weight.requires_grad:
-                    m.attach_head_shadow(lin, self._shadow_view(lin.weight))
+                    m.attach_head_shadow(lin, self._shadow_view(lin.weight, S))
 
     def _check_bindings(self):
         """`p.data` / `p.grad` must still be the views into P / G the kernels update: `model.zero_grad()` (set_to_none),
         `load_state_dict(assign=True)` or `.to()` would silently detach them.  Re-bind gradients, refuse moved params."""
+        if self._ema_scope:
+            raise RuntimeError('the model reads the averaged weights (inside `with trainer.ema_weights():`): leave the scope first')
         for p, o in zip(self.params, self.offsets):
             if p.data_ptr() != self.P.data_ptr() + 4 * o:
                 raise RuntimeError('a parameter no longer lives in FlatTrainer.P (moved by .to() / load_state_dict(assign=True)); '
@@ -212,7 +229,7 @@ class FlatTrainer:
                 if stray is not None:  # gradients were accumulated into a detached tensor this step: fold them in
                     p.grad.add_(stray)
                     if self._lazy is not None and o == self._lazy['lo']:
-                        self._lazy_mark(None)  # rows the id log does not know about
+                        self._lazy_mark(None)  # rows the id log does not know about (every flag up: the EMA sweeps the table too)
 
     # --------------------------------------------------------------------------------------------- checkpoint
     def state_dict(self):
@@ -230,6 +247,8 @@ class FlatTrainer:
         fe = getattr(self.model, 'frontend', None)
         if fe is not None and hasattr(fe, 'state_dict'):
             out['frontend'] = fe.state_dict()
+        if self.E is not None:
+            out['ema'] = {'decay': self.ema_decay, 'warmup': self.ema_warmup, 'weights': self.ema_state_dict()}
         return out
 
     def load_state_dict(self, sd):
@@ -260,6 +279,14 @@ class FlatTrainer:
             steps.add(int(float(st['step'])))
         if len(steps) > 1:
             raise ValueError('per-parameter step counts differ')
+        ema = sd.get('ema') if self.E is not None else None  # (an 'ema' entry given to a trainer without EMA is ignored)
+        if ema is not None:
+            w = ema['weights']
+            if sorted(w) != sorted(self.names):
+                raise ValueError(f'EMA weights were saved for a different set of parameters: {sorted(set(w) ^ set(self.names))[:6]} ...')
+            for name, p in zip(self.names, self.params):
+                if tuple(w[name].shape) != tuple(p.shape):
+                    raise ValueError(f'EMA weights entry {name}: shape {tuple(w[name].shape)}, the parameter {tuple(p.shape)}')
         for o, n, st in loaded:
             self.M[o:o + n].copy_(st['exp_avg'].reshape(-1))
             self.V[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
@@ -277,15 +304,84 @@ class FlatTrainer:
             lo, hi = z['lo'], z['lo'] + z['rows'] * z['rowlen']
             live = (self.M[lo:hi].view(z['rows'], -1).abs().amax(1) > 0) | (self.V[lo:hi].view(z['rows'], -1).amax(1) > 0)
             z['flags'].copy_(live.to(torch.uint8) | z['flags'])
+        if ema is not None:  # the averaged weights as saved; the decay and the warm-up stay the constructor's
+            for name, o, p in zip(self.names, self.offsets, self.params):
+                self.E[o:o + p.numel()].copy_(ema['weights'][name].reshape(-1))
+            self._ema_primed = True
+            self._ema_flag_rows()
+        elif self.E is not None:  # a checkpoint without averaged weights: E is primed again from the weights as they stand
+            self.ema_reset()
 
     def refresh_shadows(self):
         """Call after writing parameters behind the trainer's back (model.load_state_dict): re-cast the bf16 shadow."""
+        if self._ema_scope:
+            raise RuntimeError('refresh_shadows() inside `with trainer.ema_weights():`: leave the scope first')
         if self.S is not None:
             ops.cast_bf16(self.P, self.S)
             self._attach_shadows()
+        self._ema_flag_rows()
+
+    # ------------------------------------------------------------------------------------------------ weight EMA
+    def ema_decay_at(self, t):
+        """The decay the device applies at the t-th optimiser step (t >= 1 counts finished steps, that one included), as the fp32
+        value: d = min(decay, (1 + t) / (10 + t)) with ema_warmup, else decay -- each operation one fp32 operation (csrc/ema.hip)."""
+        if self.E is None:
+            raise RuntimeError('this trainer keeps no EMA (ema_decay=None)')
+        d = torch.tensor(self.ema_decay, dtype=torch.float32)
+        if self.ema_warmup:
+            t32 = torch.tensor(float(t), dtype=torch.float32)
+            one, ten = torch.tensor(1.0, dtype=torch.float32), torch.tensor(10.0, dtype=torch.float32)
+            d = torch.minimum(d, (one + t32) / (ten + t32))
+        return float(d)
+
+    def _ema_prime(self):
+        """E <- P, once: at the first step() (before Adam) or the first reader of E, whichever comes first -- so whatever rewrote the
+        weights before training started (broadcast_parameters, model.load_state_dict + refresh_shadows) is in E without a call."""
+        if self.E is None:
+            raise RuntimeError('this trainer keeps no EMA (ema_decay=None)')
+        if not self._ema_primed:
+            if self.E.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('the EMA would be primed inside a stream capture; GraphedStep primes it before it captures')
+            self.E.copy_(self.P)
+            self._ema_primed = True
+
+    def ema_reset(self):
+        """Forget the average: the next step() (or reader) primes E from the weights as they stand then."""
+        if self.E is None:
+            raise RuntimeError('this trainer keeps no EMA (ema_decay=None)')
+        if self._ema_scope:
+            raise RuntimeError('ema_reset() inside `with trainer.ema_weights():`: leave the scope first')
+        self._ema_primed = False
+
+    def _ema_flag_rows(self):
+        """The EMA kernel skips the unflagged rows of the lazy table, which is exact while E == P there, bit for bit.  After P or E
+        was written outside step() (refresh_shadows, load_state_dict): raise the flag of every row that holds a difference.  A raised
+        flag is always safe: Adam leaves a row without gradient and moments as it is."""
+        z = self._lazy
+        if self.E is None or not self._ema_primed or z is None:
+            return
+        lo, hi = z['lo'], z['lo'] + z['rows'] * z['rowlen']
+        differ = (self.E[lo:hi].view(torch.int32) != self.P[lo:hi].view(torch.int32)).view(z['rows'], -1).any(1)
+        z['flags'].copy_(differ.to(torch.uint8) | z['flags'])
+
+    def ema_state_dict(self):
+        """{name: tensor} of the trainable parameters, taken from E (clones, parameter shapes): what
+        `other_model.load_state_dict(..., strict=False)` takes to run another copy of the model on the averaged weights."""
+        self._ema_prime()
+        return {n: self.E[o:o + p.numel()].view(p.shape).clone() for n, o, p in zip(self.names, self.offsets, self.params)}
+
+    def ema_weights(self):
+        """`with trainer.ema_weights():` -- the model runs on the averaged weights inside the block (sampling, evaluation) and on the
+        trained ones after it.  Entry points every flat parameter's `.data` at its view of E, casts E into its bf16 shadow ES (on
+        EVERY entry: the bf16 copies can never be older than E) and hands the tower and the heads views of ES; exit puts the views
+        of P and S back.  `p.grad` keeps pointing into G.  Frozen weights are not touched.  Inside the block step(), zero_grad(),
+        refresh_shadows(), a GraphedStep call and a second scope raise: they would train P while the model reads E."""
+        return _EmaScope(self)
 
     # ---------------------------------------------------------------------------------------------
     def zero_grad(self):
+        if self._ema_scope:
+            raise RuntimeError('zero_grad() inside `with trainer.ema_weights():`: the model reads the averaged weights; leave the scope first')
         z = self._lazy
         if z is not None:
             # Table rows a backward wrote that no step() recorded as dirty (a step skipped on a non-finite loss; a backward whose forward
@@ -480,9 +576,13 @@ class FlatTrainer:
 
     def step(self):
         """clip_grad_norm_(max_norm) + Adam (train.py:324-325) on the averaged gradients."""
+        if self._ema_scope:
+            raise RuntimeError('step() inside `with trainer.ema_weights():`: the model reads the averaged weights; leave the scope first')
         if _lib.is_deterministic():
             refuse_unproven_width(self.model, 'a deterministic-mode trainer step')
         self._check_bindings()
+        if self.E is not None:
+            self._ema_prime()  # (before Adam: the average starts from the weights this step starts from)
         self.allreduce_grads()
         if self._lazy is not None:
             ids = self.model.sparse_grad_rows().get(self._lazy['name'])
@@ -507,12 +607,52 @@ class FlatTrainer:
         ops.grad_sqnorm(self.G, self._sq, partials=self._sq_partials, lazy=self._lazy_arg())
         ops.adam_step(self.P, self.G, self.M, self.V, self.S, self.step_count, self.lr, self.betas, self.eps, self.wd,
                       self.max_norm, self._sq, gscale, step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg())
+        if self.E is not None:  # same stream, after Adam; t is read from the device counter: a captured step carries it as it stands
+            ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, step_dev=self._step_dev, lazy=self._lazy_arg())
         tw = getattr(self.model, 'transformer', None)
         if tw is not None and hasattr(tw, 'mark_shadow_fresh') and getattr(self, '_tower_shadow_attached', False):
             tw.mark_shadow_fresh()  # the Adam kernel wrote the attached bf16 views; an un-attached tower recasts itself
 
     def grad_norm(self):
         return float(self.G.norm()) / self.world
+
+
+class _EmaScope:
+    """FlatTrainer.ema_weights()."""
+
+    def __init__(self, trainer):
+        self.tr = trainer
+
+    def _point(self, flat, shadow):
+        tr = self.tr
+        for p, o in zip(tr.params, tr.offsets):
+            p.data = flat[o:o + p.numel()].view(p.shape)
+        if shadow is not None:
+            tr._attach_shadows(shadow)
+
+    def __enter__(self):
+        tr = self.tr
+        if tr.E is None:
+            raise RuntimeError('this trainer keeps no EMA (ema_decay=None)')
+        if tr._ema_scope:
+            raise RuntimeError('`with trainer.ema_weights():` is already active: the scope does not nest')
+        if tr.E.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('`with trainer.ema_weights():` inside a stream capture: a replay would not switch the weights')
+        tr._check_bindings()
+        tr._ema_prime()
+        if tr.S is not None:
+            if tr.ES is None:
+                tr.ES = torch.empty_like(tr.S)
+            ops.cast_bf16(tr.E, tr.ES)
+        self._point(tr.E, tr.ES)
+        tr._ema_scope = True
+        return tr
+
+    def __exit__(self, *exc):
+        tr = self.tr
+        self._point(tr.P, tr.S)
+        tr._ema_scope = False
+        return False
 
 
 class GraphedStep:
@@ -542,6 +682,10 @@ class GraphedStep:
         self.graph, self.capture_error = None, None
         # a captured graph keeps the kernels of the mode it was captured with: recorded here, checked at every replay
         self.deterministic = _lib.is_deterministic()
+        if trainer.E is not None:
+            if trainer._ema_scope:
+                raise RuntimeError('GraphedStep inside `with trainer.ema_weights():`: leave the scope first')
+            trainer._ema_prime()  # before the warm-up: the copy E <- P is never captured
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # warm-up on a side stream, as graph capture requires (real training steps)
@@ -587,6 +731,9 @@ class GraphedStep:
         return loss.detach()
 
     def __call__(self, **inputs):
+        if self.trainer._ema_scope:
+            raise RuntimeError('a GraphedStep call inside `with trainer.ema_weights():`: the replay would train P while the model reads '
+                               'the averaged weights; leave the scope first')
         if _lib.is_deterministic() != self.deterministic:
             raise RuntimeError(f'this GraphedStep was captured with deterministic={self.deterministic} and is called with '
                                f'deterministic={_lib.is_deterministic()}: a replay would run the other mode\'s kernels; switch back '

@@ -483,6 +483,18 @@ def adam_step(p, g, m, v, shadow, step, lr, betas=(0.9, 0.999), eps=1e-8, weight
          float(grad_scale), _p(fl), int(lo), int(rows), int(rowlen), _stream())
 
 
+def ema_update(ema, p, decay, warmup, step, step_dev=None, lazy=None):
+    """ema <- fmaf(1 - d, p - ema, ema) over the flat fp32 buffers, d = decay or (warmup) min(decay, (1 + t) / (10 + t)) with t the
+    count of finished steps (`step`, or the device scalar step_dev); lazy as in adam_step: unflagged rows are not touched
+    (include/mmvid_hip_ext.h: mmvid_ema_update)."""
+    _chk(ema, f32, 'ema'), _chk(p, f32, 'p')
+    if ema.numel() != p.numel():
+        raise ValueError(f'ema_update: ema has {ema.numel()} elements, p {p.numel()}')
+    fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
+    call('mmvid_ema_update', _p(ema), _p(p), p.numel(), float(decay), int(bool(warmup)), int(step), _p(step_dev), _p(fl), int(lo),
+         int(rows), int(rowlen), _stream())
+
+
 def lr_schedule(step_dev, kind, lr_min, lr_max, warmup, every, lr_out):
     call('mmvid_lr_schedule', _p(step_dev), int(kind), float(lr_min), float(lr_max), int(warmup), int(every), _p(lr_out),
          _stream())
