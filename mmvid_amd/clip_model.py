@@ -10,6 +10,7 @@ from torch import nn
 
 from . import _lib, ops
 from .clip_tower import OpenAICLIPTransformer, _Holder, _ln_params
+from .shadow import Cached
 
 f32, bf16 = torch.float32, torch.bfloat16
 IMAGE_SLICE = 256  # frames per pass through the visual tower at 50 positions (bounds the tower's scratch: frames_per_pass; results do not depend on it)
@@ -69,8 +70,7 @@ class CLIP(nn.Module):
         for k, v in (('input_resolution', image_resolution), ('context_length', context_length), ('vocab_size', vocab_size)):
             self.register_buffer(k, torch.tensor(v, dtype=torch.int64), persistent=False)
         self._shape = dict(R=image_resolution, P=vision_patch_size, L=context_length, V=vocab_size, D=embed_dim)
-        self._conv_bf16 = None
-        self._conv_key = None
+        self._conv_bf16 = Cached(self._conv_sources, self._build_conv_weight)
 
     @property
     def dtype(self):
@@ -117,17 +117,19 @@ class CLIP(nn.Module):
     def _conv_weight(self):
         """bf16 copy of conv1.weight as the patch GEMM's [width, Kp] operand (columns beyond 3*P*P zero: see patch_columns), rebuilt
         when the parameter changes."""
+        return self._conv_bf16.get()
+
+    def _conv_sources(self):
+        return [self.visual.conv1.weight]
+
+    def _build_conv_weight(self):
         w = self.visual.conv1.weight
-        key = (w._version, w.data_ptr(), w.device)
-        if self._conv_key != key:
-            flat = ops.cast_bf16(w.detach().contiguous().view(w.shape[0], -1))
-            Kp = patch_columns(self._shape['P'])
-            if Kp != flat.shape[1]:
-                flat, dense = torch.zeros(w.shape[0], Kp, device=w.device, dtype=bf16), flat
-                flat[:, :dense.shape[1]] = dense
-            self._conv_bf16 = flat
-            self._conv_key = key
-        return self._conv_bf16
+        flat = ops.cast_bf16(w.detach().contiguous().view(w.shape[0], -1))
+        Kp = patch_columns(self._shape['P'])
+        if Kp != flat.shape[1]:
+            flat, dense = torch.zeros(w.shape[0], Kp, device=w.device, dtype=bf16), flat
+            flat[:, :dense.shape[1]] = dense
+        return flat
 
     def _check_image(self, image, normalize):
         R = self._shape['R']

@@ -12,6 +12,7 @@ from torch import nn
 
 from . import _lib, ops
 from .functional import _note_params, _with_param_zeros
+from .shadow import Bf16Weight
 
 TOWER_SHAPES = {  # which_model -> (width, layers, heads), clip_model.py:538-541 with ViT-B/32
     'openai_clip_visual': (768, 12, 12),
@@ -249,8 +250,10 @@ class OpenAICLIPTransformer(nn.Module):
         self.mask_spec = self.build_attention_mask(seq_len, mask_type, **(mask_kwargs or {})) if causal else None
         if model_path is not None:
             self.load_clip_checkpoint(model_path, which_model, sd)
-        self._shadow = None  # flat bf16 copy of the matrix weights
-        self._shadow_key = None
+        # where the four matrices of every layer live: the per-forward walk reads 48 attributes instead of 132 (_matrix_params)
+        self._matrix_holders = [h for blk in self.transformer.resblocks for h in (
+            (blk.attn, 'in_proj_weight'), (blk.attn.out_proj, 'weight'), (blk.mlp.c_fc, 'weight'), (blk.mlp.c_proj, 'weight'))]
+        self._bf16 = [None] * len(self._matrix_holders)  # bf16_weights()
         self._scratch = None
         self._scratch_retired = []
         self.backward_chunk_layers = int(os.environ.get('MMVID_BWD_CHUNK', 0))  # the backward returns to the host every N layers (0: planned, see backward_chunks) ...
@@ -337,32 +340,26 @@ class OpenAICLIPTransformer(nn.Module):
         return any(p.requires_grad for p in self.parameters())
 
     def _matrix_params(self):
-        for blk in self.transformer.resblocks:
-            yield blk.attn.in_proj_weight
-            yield blk.attn.out_proj.weight
-            yield blk.mlp.c_fc.weight
-            yield blk.mlp.c_proj.weight
+        for holder, name in self._matrix_holders:
+            yield getattr(holder, name)
 
-    def attach_shadow(self, views):
-        """Engine hook: `views` = list of bf16 tensors (one per matrix param, in _matrix_params order) that an
-        external fused optimiser keeps equal to bf16(param)."""
-        self._shadow = list(views)
-        self.mark_shadow_fresh()
+    def bf16_weights(self):
+        """One shadow.Bf16Weight per matrix, in _matrix_params() order: what the kernels read, and what engine.FlatTrainer attaches
+        views of its flat bf16 buffer to.  Made at first use, and again for a Parameter object that was replaced
+        (load_state_dict(assign=True)), in the one pass over the matrices that every forward makes."""
+        ws = self._bf16
+        for i, p in enumerate(self._matrix_params()):
+            if ws[i] is None or ws[i].param is not p:
+                ws[i] = Bf16Weight(p)
+        return ws
 
     def mark_shadow_fresh(self):
-        self._shadow_key = tuple((p._version, p.data_ptr()) for p in self._matrix_params())
+        """Whoever keeps attached views current (the Adam kernel; a restore of the trainer's flat buffers) has just written them."""
+        for w in self.bf16_weights():
+            w.mark_fresh()
 
     def _sync_shadow(self):
-        ps = list(self._matrix_params())
-        key = tuple((p._version, p.data_ptr()) for p in ps)
-        if self._shadow is None or self._shadow[0].device != ps[0].device:
-            self._shadow = [torch.empty(p.shape, device=p.device, dtype=torch.bfloat16) for p in ps]
-            self._shadow_key = None
-        if key != self._shadow_key:
-            for p, s in zip(ps, self._shadow):
-                ops.cast_bf16(p.detach().contiguous(), s)
-            self._shadow_key = key
-        return self._shadow
+        return [w.get() for w in self.bf16_weights()]
 
     def _cfg(self, B, L):
         c = _lib.TowerCfg()

@@ -20,6 +20,7 @@ from .dalle_bert import DivideMax, eval_decorator, exists, set_requires_grad
 from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import AssembleSequence, LNLinear, LNLinearCrossEntropy
 from .modules import AxialPositionalEmbedding, AxialPositionalEmbeddingList
+from .shadow import Bf16Weight
 
 NEG = -torch.finfo(torch.float32).max
 
@@ -90,7 +91,7 @@ class DALLE(nn.Module):
         self.loss_vis_weight, self.loss_img_weight = 1., loss_img_weight
         self.eraser = dict(p=1.0, scale=(0.4, 0.8), ratio=(0.5, 2.0))  # RandomErasing(value=-1), dalle_artv.py:229-232
         self.frontend = Frontend(seed=kwargs.get('frontend_seed'))
-        self._w16_cache = None
+        self._head_bf16 = None  # bf16_weights()
         # (artv_sampling.token_launch_loop: reads the failure flag every so many tokens; tests: hook(tokens launched so far, session) after every launch)
         self._decode_check_every, self._token_step_hook = 64, None
         seg = [0] * (text_seq_len + 1) + [1] * self.visual_seq_len + [2] * self.target_seq_len
@@ -129,28 +130,14 @@ class DALLE(nn.Module):
 
     # ---- bf16 copy of the 51,584 x 768 head ----------------------------------------------------------------------------
     def _w16(self):
+        return self.bf16_weights()[0].get()
+
+    def bf16_weights(self):
+        """As BERT.bf16_weights, for the one head: its shadow.Bf16Weight, made at first use and again if its Parameter object was replaced."""
         w = self.to_logits[1].weight
-        c = self._w16_cache
-        if c is not None and c[0] == 'attached':
-            if c[2] == w.data_ptr():
-                if c[3] != w._version:  # written through torch since the attachment: refresh the attached view
-                    ops.cast_bf16(w.detach().contiguous(), c[1])
-                    self._w16_cache = ('attached', c[1], c[2], w._version)
-                return c[1]
-            c = None
-        key = (w._version, w.data_ptr())
-        if c is None or c[0] != key:
-            c = self._w16_cache = (key, ops.cast_bf16(w.detach().contiguous()))
-        return c[1]
-
-    def attach_head_shadow(self, lin, view):
-        """Engine hook (see BERT.attach_head_shadow): a fused optimiser updates parameters through raw pointers, which
-        never bumps `_version`; it keeps `view` == bf16(weight) itself."""
-        assert lin is self.to_logits[1]
-        self._w16_cache = ('attached', view, lin.weight.data_ptr(), lin.weight._version)
-
-    def head_shadow_targets(self):
-        return [self.to_logits[1]]
+        if self._head_bf16 is None or self._head_bf16.param is not w:
+            self._head_bf16 = Bf16Weight(w)
+        return [self._head_bf16]
 
     # ---- token helpers (dalle_artv.py:306-416) --------------------------------------------------------------------------
     def get_image_tokens(self, image, reshape=True, insert_sep=False, which_vae='vae'):

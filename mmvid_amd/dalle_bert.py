@@ -25,6 +25,7 @@ from . import ops, sampling, seeded
 from .clip_tower import OpenAICLIPTransformer, check_tower_width
 from .frontend import Frontend, check_condition_drop, face_choices
 from .functional import PosTable, AssembleSequence, BertHeads, LNLinear, Linear, LayerNormRows
+from .shadow import Bf16Weight
 from .modules import AxialPositionalEmbedding, AxialPositionalEmbeddingList
 
 
@@ -158,7 +159,7 @@ class BERT(nn.Module):
         self.to_logits_vid = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, 1))
         self.current_step = 0
         self.frontend = Frontend(seed=kwargs.get('frontend_seed'))  # None: torch.initial_seed() + rank at first use (train.py:87)
-        self._w16_cache = {}
+        self._head_bf16 = [None] * len(self.head_shadow_targets())  # bf16_weights()
         self._row_cache = {}
         self._debug_keep = None
         self._text_id_log, self._text_id_overflow = [], False
@@ -176,33 +177,24 @@ class BERT(nn.Module):
 
     # ------------------------------------------------------------------------------------ small helpers
     def _w16(self, lin):
-        """bf16 copy of a head's Linear weight: the view a fused optimiser keeps current (attach_head_shadow), else a
-        cast refreshed whenever the parameter's storage or version changes."""
-        w = lin.weight
-        c = self._w16_cache.get(id(lin))
-        if c is not None and c[0] == 'attached':
-            if c[2] == w.data_ptr():
-                if c[3] != w._version:  # written through torch (load_state_dict, an in-place op): refresh the view itself
-                    ops.cast_bf16(w.detach().contiguous(), c[1])
-                    self._w16_cache[id(lin)] = ('attached', c[1], c[2], w._version)
-                return c[1]
-            c = None  # the parameter moved (.to(), load_state_dict(assign=True)): the attachment is void
-        key = (w._version, w.data_ptr())
-        if c is None or c[0] != key:
-            c = (key, ops.cast_bf16(w.detach().contiguous()))
-            self._w16_cache[id(lin)] = c
-        return c[1]
-
-    def attach_head_shadow(self, lin, view):
-        """Engine hook: `view` is kept equal to bf16(lin.weight) by the fused optimiser for as long as the parameter
-        stays in the trainer's flat buffer (same data_ptr)."""
-        self._w16_cache[id(lin)] = ('attached', view, lin.weight.data_ptr(), lin.weight._version)
+        """bf16 copy of a head's Linear weight (shadow.Bf16Weight: the view engine.FlatTrainer keeps current, else a cast of its own)."""
+        at = [i for i, head in enumerate(self.head_shadow_targets()) if head is lin]
+        if not at:
+            raise ValueError('_w16: not one of the Linear layers of head_shadow_targets()')
+        return self.bf16_weights()[at[0]].get()
 
     def head_shadow_targets(self):
-        """Linear layers whose weight the MFMA kernels read in bf16 (engine.FlatTrainer attaches shadow views)."""
+        """Linear layers whose weight the MFMA kernels read in bf16."""
         m = self.text_feature_mapping
         extra = [] if m is None else ([m] if isinstance(m, nn.Linear) else [m[1], m[3]])
         return [self.to_logits[1]] + extra
+
+    def bf16_weights(self):
+        """One shadow.Bf16Weight per head of head_shadow_targets(), in that order, made at first use.  (A Parameter object that was
+        replaced -- load_state_dict(assign=True) -- gets a new one.)"""
+        self._head_bf16 = [w if w is not None and w.param is lin.weight else Bf16Weight(lin.weight)
+                           for w, lin in zip(self._head_bf16, self.head_shadow_targets())]
+        return self._head_bf16
 
     def _tables(self):
         vis = self.visual_emb.weight if (self.num_visuals > 0 and self.visual_emb is not None) else self.image_emb.weight

@@ -110,6 +110,7 @@ class FlatTrainer:
             self.P[o:o + n].copy_(p.detach().reshape(-1))
             p.data = self.P[o:o + n].view(p.shape)
             p.grad = self.G[o:o + n].view(p.shape)
+        self._attached = []  # the shadow.Bf16Weights that read views of S (_attach_shadows)
         if self.S is not None:
             ops.cast_bf16(self.P, self.S)
             self._attach_shadows()
@@ -196,23 +197,23 @@ class FlatTrainer:
         return (self.S if S is None else S)[o:o + p.numel()].view(p.shape)
 
     def _attach_shadows(self, S=None):
-        """Hand the model views of the flat bf16 shadow for every weight its MFMA kernels read in bf16: the tower's
-        matrices and each head listed by `model.head_shadow_targets()` (BERT: to_logits; ART-V: the 51,584-way to_logits).
-        A weight that is frozen (not in the flat buffer) keeps the model's own cast-on-change copy.  S: the flat bf16 buffer the
-        views are taken from (default self.S; `ema_weights()` passes the shadow of the averaged weights).  The model records each
-        parameter's data_ptr with the view, so the parameters must already point where they will be read from."""
-        m = self.model
-        self._tower_shadow_attached = False
-        tw = getattr(m, 'transformer', None)
-        if tw is not None and hasattr(tw, 'attach_shadow') and all(p.requires_grad for p in tw._matrix_params()):
-            tw.attach_shadow([self._shadow_view(p, S) for p in tw._matrix_params()])
-            self._tower_shadow_attached = True
-        elif tw is not None and hasattr(tw, '_shadow_key'):
-            tw._shadow_key = None  # a tower that casts for itself is keyed on (version, data_ptr): neither sees a kernel's write
-        if hasattr(m, 'attach_head_shadow') and hasattr(m, 'head_shadow_targets'):
-            for lin in m.head_shadow_targets():
-                if lin.weight.requires_grad:
-                    m.attach_head_shadow(lin, self._shadow_view(lin.weight, S))
+        """Every weight the MFMA kernels read in bf16 is a shadow.Bf16Weight, listed by the `bf16_weights()` of the module that owns
+        it (the tower: its matrices; BERT / ART-V: their heads).  One whose parameter lives in the flat buffer is handed its view of
+        the flat bf16 shadow, which step() keeps current; every other one (frozen) is told to cast again for itself.  S: the flat bf16
+        buffer the views are taken from (default self.S; `ema_weights()` passes the shadow of the averaged weights).  An attachment
+        records the parameter's data_ptr, so the parameters must already point where they will be read from.  The walk is over
+        `model.modules()`: a model that only holds a tower (no `bf16_weights()` of its own) is served, and so is every tower
+        registered anywhere below the model, not only `model.transformer`."""
+        flat = {id(p) for p in self.params}
+        self._attached, self._tower_shadow_attached = [], False
+        for mod in self.model.modules():
+            for w in getattr(mod, 'bf16_weights', list)():
+                if id(w.param) in flat:
+                    w.attach(self._shadow_view(w.param, S))
+                    self._attached.append(w)
+                    self._tower_shadow_attached |= mod is getattr(self.model, 'transformer', None)  # (read by bench.py)
+                else:
+                    w.invalidate()
 
     def _check_bindings(self):
         """`p.data` / `p.grad` must still be the views into P / G the kernels update: `model.zero_grad()` (set_to_none),
@@ -609,9 +610,8 @@ class FlatTrainer:
                       self.max_norm, self._sq, gscale, step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg())
         if self.E is not None:  # same stream, after Adam; t is read from the device counter: a captured step carries it as it stands
             ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, step_dev=self._step_dev, lazy=self._lazy_arg())
-        tw = getattr(self.model, 'transformer', None)
-        if tw is not None and hasattr(tw, 'mark_shadow_fresh') and getattr(self, '_tower_shadow_attached', False):
-            tw.mark_shadow_fresh()  # the Adam kernel wrote the attached bf16 views; an un-attached tower recasts itself
+        for w in self._attached:
+            w.mark_fresh()  # the Adam kernel wrote the attached bf16 views (a weight that is not attached is frozen: no kernel writes it)
 
     def grad_norm(self):
         return float(self.G.norm()) / self.world

@@ -19,6 +19,7 @@ from torch import nn
 
 from . import _lib, ops
 from . import prd_score as prd
+from .shadow import Cached
 
 bf16, f32 = torch.bfloat16, torch.float32
 
@@ -78,7 +79,7 @@ class InceptionI3d(nn.Module):
             self.add_module(name, InceptionModule(cin, c))
             cin = c[0] + c[2] + c[4] + c[5]
         self.logits = Unit3D(cin, num_classes, bn=False)
-        self._shadow, self._shadow_key, self._arenas = None, None, {}
+        self._shadow, self._arenas = Cached(self._shadow_sources, self._build_shadow), {}
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -89,15 +90,13 @@ class InceptionI3d(nn.Module):
         s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
         return w * s.view(-1, 1, 1, 1, 1), bn.bias.detach().float() - bn.running_mean.detach().float() * s
 
-    def _sync_shadow(self):
-        """bf16 weights [Cout][kt][kh][kw][Cin] with BatchNorm folded in and fp32 biases, built on first use (and again only when a
-        parameter changes).  The stem's is [64][7][7][24]: (kw, c) folded into the channel axis as the preprocess writes it; the three
-        1x1x1 branches of a block that read its input (b0, b1a, b2a) are one weight [c0 + c1 + c3][Cin]."""
-        ps = list(self.parameters()) + list(self.buffers())
-        key = tuple((p._version, p.data_ptr(), str(p.device)) for p in ps)
-        if key == self._shadow_key:
-            return self._shadow
+    def _shadow_sources(self):
+        return list(self.parameters()) + list(self.buffers())
 
+    def _build_shadow(self):
+        """bf16 weights [Cout][kt][kh][kw][Cin] with BatchNorm folded in and fp32 biases, built on first use (and again only when a
+        parameter or buffer changes: self._shadow).  The stem's is [64][7][7][24]: (kw, c) folded into the channel axis as the preprocess
+        writes it; the three 1x1x1 branches of a block that read its input (b0, b1a, b2a) are one weight [c0 + c1 + c3][Cin]."""
         def lay(w):
             return ops.cast_bf16(w.permute(0, 2, 3, 4, 1).contiguous())
 
@@ -117,7 +116,6 @@ class InceptionI3d(nn.Module):
             sh[name + '.b1b'], sh[name + '.b2b'], sh[name + '.b3b'] = unit(m.b1b), unit(m.b2b), unit(m.b3b)
         sh['logits'] = (self.logits.conv3d.weight.detach().float().reshape(self.num_classes, -1).contiguous(),
                         self.logits.conv3d.bias.detach().float().contiguous())
-        self._shadow, self._shadow_key = sh, key
         return sh
 
     # ---- plan ------------------------------------------------------------------------------------------------------------------
@@ -191,7 +189,7 @@ class InceptionI3d(nn.Module):
         return self._head(arena)
 
     def _run_plan(self, arena, plan):
-        sh = self._sync_shadow()
+        sh = self._shadow.get()
         bufs, B, st = arena['bufs'], arena['B'], ops._stream()
         for op in plan:
             if op[0] == 'conv':
@@ -214,7 +212,7 @@ class InceptionI3d(nn.Module):
     def _head(self, arena):
         bufs, B, st = arena['bufs'], arena['B'], ops._stream()
         src, To, C = arena['head']
-        wl, bl = self._sync_shadow()['logits']
+        wl, bl = self._shadow.get()['logits']
         out = torch.empty(B, self.num_classes, device=bufs[src].device, dtype=f32)
         _lib.call('mmvid_i3d_head', ops._p(bufs[src]), B, To, C, ops._p(wl), ops._p(bl), self.num_classes, ops._p(out), st)
         return out

@@ -15,6 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from .shadow import Cached
 
 f32, bf16 = torch.float32, torch.bfloat16
 BOS, PAD, EOS = 0, 1, 2  # <s>, <pad>, </s>
@@ -207,7 +208,7 @@ class RobertaModel(nn.Module):
             self.encoder.layer.append(ly)
         self.pooler = _Holder()
         self.pooler.dense = _linear(E, E)  # kept for the checkpoint's keys; not computed
-        self._shadow, self._shadow_key, self._scratch = None, None, None
+        self._shadow, self._scratch = Cached(self._shadow_sources, self._build_shadow), None
 
     # ---- checkpoints --------------------------------------------------------------------------------------
     @classmethod
@@ -287,29 +288,28 @@ class RobertaModel(nn.Module):
         return RobertaModelOutput((x, ))
 
     # ---- native plumbing --------------------------------------------------------------------------------------
-    def _sync_shadow(self):
-        """bf16 GEMM operands, built once (and again only when a weight changes): per layer Q|K|V packed [3E, E] with its bias
-        [3E] fp32, attention.output.dense, intermediate.dense, output.dense."""
-        ps = [p for ly in self.encoder.layer for p in (ly.attention.self.query.weight, ly.attention.self.key.weight,
-                                                       ly.attention.self.value.weight, ly.attention.self.query.bias,
-                                                       ly.attention.self.key.bias, ly.attention.self.value.bias,
-                                                       ly.attention.output.dense.weight, ly.intermediate.dense.weight,
-                                                       ly.output.dense.weight)]
-        key = tuple((p._version, p.data_ptr(), str(p.device)) for p in ps)
-        if key != self._shadow_key:
-            sh = []
-            for ly in self.encoder.layer:
-                s = ly.attention.self
-                qkv_w = torch.cat([s.query.weight, s.key.weight, s.value.weight]).detach().contiguous()
-                qkv_b = torch.cat([s.query.bias, s.key.bias, s.value.bias]).detach().float().contiguous()
-                sh.append((ops.cast_bf16(qkv_w), qkv_b, ops.cast_bf16(ly.attention.output.dense.weight.detach().contiguous()),
-                           ops.cast_bf16(ly.intermediate.dense.weight.detach().contiguous()),
-                           ops.cast_bf16(ly.output.dense.weight.detach().contiguous())))
-            self._shadow, self._shadow_key = sh, key
-        return self._shadow
+    def _shadow_sources(self):
+        return [p for ly in self.encoder.layer for p in (ly.attention.self.query.weight, ly.attention.self.key.weight,
+                                                         ly.attention.self.value.weight, ly.attention.self.query.bias,
+                                                         ly.attention.self.key.bias, ly.attention.self.value.bias,
+                                                         ly.attention.output.dense.weight, ly.intermediate.dense.weight,
+                                                         ly.output.dense.weight)]
+
+    def _build_shadow(self):
+        """bf16 GEMM operands (built once, and again only when a weight changes: self._shadow): per layer Q|K|V packed [3E, E] with
+        its bias [3E] fp32, attention.output.dense, intermediate.dense, output.dense."""
+        sh = []
+        for ly in self.encoder.layer:
+            s = ly.attention.self
+            qkv_w = torch.cat([s.query.weight, s.key.weight, s.value.weight]).detach().contiguous()
+            qkv_b = torch.cat([s.query.bias, s.key.bias, s.value.bias]).detach().float().contiguous()
+            sh.append((ops.cast_bf16(qkv_w), qkv_b, ops.cast_bf16(ly.attention.output.dense.weight.detach().contiguous()),
+                       ops.cast_bf16(ly.intermediate.dense.weight.detach().contiguous()),
+                       ops.cast_bf16(ly.output.dense.weight.detach().contiguous())))
+        return sh
 
     def _layer_structs(self):
-        sh = self._sync_shadow()
+        sh = self._shadow.get()
         arr = (_lib.PostLnLayer * len(self.encoder.layer))()
         keep = []
 

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from . import ops, vqgan_plan
+from .shadow import Cached
 
 f32 = torch.float32
 
@@ -163,16 +164,17 @@ class VQGanVAE1024(nn.Module):
         # are 97-100 % of the reference's either way); 'bf16_all' = the decoder's as well; 'f32' = fp32
         # residual streams (rounds 1-4)
         self.stream = os.environ.get('MMVID_VQGAN_STREAM', 'bf16')
-        self._prep = {}
-        self._prep_key = None
+        self._prep_cache = Cached(self._prep_sources, dict)
 
     # ---- weight preparation (cached) ----------------------------------------------------------------
+    def _prep_sources(self):
+        return self.model.parameters()
+
     def _prepared(self):
-        key = tuple((p._version, p.data_ptr()) for p in self.model.parameters())
-        if key != self._prep_key:
-            self._prep = {}
-            self._prep_key = key
-        return self._prep
+        """The dict that _cw / _cw_qkv / _ee / _plan fill: a new, empty one whenever a parameter has changed."""
+        return self._prep_cache.get()
+
+    _prep = property(_prepared)  # (the same dict under the attribute name it had before: callers clear it between plans)
 
     def _cw(self, holder, form='bf16'):
         """conv holder -> (w [Cout_p, taps, Cin_p], bias f32 [Cout_p], Cout), the weights laid out for the kernels of one operator:

@@ -888,6 +888,53 @@ def test_artv_flat_trainer_keeps_head_shadow_current(golden):
     assert torch.isfinite(m(text, visual=vt, target=tt, return_loss=True, vc_mode='shape_4x4')[0])
 
 
+def test_partly_frozen_tower_trains_on_current_weights():
+    """A tower with layer 0's matrices frozen under FlatTrainer: the Adam kernel writes the trained matrices through raw pointers
+    (no version moves), so their bf16 operands must be the trainer's views -- after every step, inside the EMA scope, after it."""
+    from mmvid_amd.clip_tower import OpenAICLIPTransformer
+    from mmvid_amd.engine import FlatTrainer
+    torch.manual_seed(0)
+    m = torch.nn.Module()
+    m.transformer = OpenAICLIPTransformer(32, 'openai_clip_text', layers=2)
+    m.to(DEV).train()
+    tw = m.transformer
+    ps = list(tw._matrix_params())
+    assert len(ps) == 8 and ps[0].shape == (3 * 512, 512)
+    for p in ps[:4]:
+        p.requires_grad_(False)
+    frozen = [p.detach().bfloat16() for p in ps[:4]]
+    tr = FlatTrainer(m, lr=1e-3, ema_decay=0.5)
+    x = torch.randn(2, 32, 512, device=DEV)
+    gy = torch.randn(2, 32, 512, device=DEV)
+
+    def check(flat, what):
+        """every operand is the bf16 of its parameter as it stands; a trained one that of its rows of `flat`, a frozen one unchanged"""
+        sh = tw._sync_shadow()
+        for i, p in enumerate(ps):
+            assert torch.equal(sh[i], p.detach().bfloat16()), (what, i)
+        for i, p in enumerate(ps[4:], 4):
+            o = tr.offsets[next(k for k, q in enumerate(tr.params) if q is p)]
+            assert torch.equal(sh[i], flat[o:o + p.numel()].view(p.shape).bfloat16()), (what, i)
+        for i in range(4):
+            assert torch.equal(sh[i], frozen[i]), (what, i)
+        return sh
+
+    for it in range(2):
+        tr.zero_grad()
+        y = tw(x)
+        (y * gy).sum().backward()
+        before = tr.P.clone()
+        tr.step()
+        assert not torch.equal(before, tr.P)
+        sh = check(tr.P, f'step {it}')
+        for i, p in enumerate(ps[4:], 4):
+            assert sh[i].data_ptr() == tr._shadow_view(p).data_ptr(), (it, i)
+    assert not torch.equal(tr.E, tr.P)
+    with tr.ema_weights():
+        check(tr.E, 'inside the scope')
+    check(tr.P, 'after the scope')
+
+
 def test_tower_with_frozen_matrices_still_backpropagates():
     from mmvid_amd.clip_tower import OpenAICLIPTransformer
     torch.manual_seed(0)

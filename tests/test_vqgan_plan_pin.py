@@ -50,9 +50,9 @@ def planned(strict, stream, kind, n, size_or_hw):
     """One plan through vae._plan(), on the CPU (tests/test_vqgan_oplist_host.py shows the same plans to mmvid_vqgan_check)."""
     v = _vae(size_or_hw if kind == 'enc' else 16 * size_or_hw)
     v.strict, v.stream = strict, stream
-    v._prep.clear()  # (prepared weights and arenas of the case before: nothing of a plan depends on them)
+    v._prepared().clear()  # (prepared weights and arenas of the case before: nothing of a plan depends on them)
     plan = v._plan(kind, n, size_or_hw)
-    v._prep.clear()
+    v._prepared().clear()
     return plan
 
 
