@@ -63,6 +63,35 @@ int mmvid_variates_fill(const int64_t* seeds, const int32_t* substream, int64_t 
 int mmvid_ema_update(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
                      const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, void* stream);
 
+/* ---- Non-finite guard: a training step whose gradient is not finite is skipped, by a verdict taken and obeyed on the device ------
+ *
+ * The rule (csrc/optim.hip; tests/guard_ref.py is the host replica).  mmvid_step_guard runs between the gradient norm and the
+ * optimiser, on their stream: one launch of one thread, plain loads and stores.  With sq = *sqnorm (the sum of squares that
+ * mmvid_grad_sqnorm* left) and skip = sq is inf or NaN (1 or 0):
+ *     guard_i[0] = skip                           the verdict the guarded entries read
+ *     guard_i[1] += skip                          steps skipped so far
+ *     guard_i[2] = skip ? guard_i[2] + 1 : 0      the current run of skipped steps
+ *     guard_i[3] += 1                             steps seen
+ *     guard_f[0] = sqrtf(sq) * grad_scale         the gradient norm the Adam kernel clips on (two fp32 operations), NaN / inf included
+ *     guard_f[1] = guard_f[0]   only if !skip     the last finite gradient norm
+ *     *step_dev += 1.f          only if !skip     the count of APPLIED steps: this call stands in for the step's mmvid_counter_add
+ * guard_i: int32 [4], guard_f: fp32 [2], step_dev: fp32 [1], all on the device, zeroed by the caller before the first step.
+ * Refused with an error (nothing launched): a NULL pointer; a pointer that is not 4-byte aligned.
+ *
+ * mmvid_adam_step_guarded / mmvid_ema_update_guarded take the arguments of mmvid_adam_step_rows (mmvid_hip.h) / mmvid_ema_update plus
+ * skip_dev, an int32 on the device (guard_i) read at execution: every thread of the kernel returns before its first load where
+ * *skip_dev != 0 -- nothing is read, nothing is written, p, m, v, the bf16 shadow and ema keep every byte.  With skip_dev NULL or
+ * *skip_dev == 0 they write the bytes of the unguarded entry (the same kernel; the unguarded entries pass NULL).  Every refusal of the
+ * unguarded entry carries over; in addition a skip_dev that is not 4-byte aligned is refused.  No atomics. */
+int mmvid_step_guard(const float* sqnorm, float grad_scale, float* step_dev, int32_t* guard_i, float* guard_f, void* stream);
+int mmvid_adam_step_guarded(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, const float* lr_dev,
+                            float beta1, float beta2, float eps, float weight_decay, int step, const float* step_dev, float max_norm,
+                            const float* sqnorm, float grad_scale, const uint8_t* row_flags, int64_t table_lo, int64_t table_rows,
+                            int rowlen, const int32_t* skip_dev, void* stream);
+int mmvid_ema_update_guarded(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
+                             const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, const int32_t* skip_dev,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,9 @@ __device__ __forceinline__ float ema_one(float a, float p, float e) {
 }
 
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float decay, int warmup,
-                                                  float t, const float* __restrict__ step_dev, LazyRows z) {
+                                                  float t, const float* __restrict__ step_dev, LazyRows z,
+                                                  const int* __restrict__ skip) {
+    if (skip && *skip) return;  // non-finite guard (mmvid_step_guard): a kernel argument's load, the same in every lane -- a scalar branch
     if (step_dev) t = *step_dev;  // step count kept on the device: a captured step follows the warm-up without host input
     float d = decay;
     if (warmup) d = fminf(decay, __fdiv_rn(__fadd_rn(1.f, t), __fadd_rn(10.f, t)));
@@ -54,8 +56,9 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const
 
 }  // namespace
 
-extern "C" int mmvid_ema_update(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
-                                const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, void* stream) {
+// mmvid_ema_update (skip_dev NULL) and mmvid_ema_update_guarded: one set of checks, one kernel
+static int ema_launch(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
+                      const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, const int32_t* skip_dev, void* stream) {
     MMVID_REQUIRE(ema && p, "ema_update: ema and p must not be NULL");
     MMVID_REQUIRE(n >= 0 && n <= (int64_t)1 << 60, "ema_update: n=%lld is negative (or beyond 2^60)", (long long)n);
     MMVID_REQUIRE((((uintptr_t)ema | (uintptr_t)p) & 15) == 0, "ema_update: buffers must be 16-byte aligned");
@@ -79,7 +82,19 @@ extern "C" int mmvid_ema_update(float* ema, const float* p, int64_t n, float dec
     long b = (long)((n + 1023) / 1024);
     if (b > 512) b = 512;  // (two blocks per CU: see the head of this file)
     hipLaunchKernelGGL(ema_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, decay, warmup != 0,
-                       (float)(step >= 1 ? step : 1), step_dev, z);
+                       (float)(step >= 1 ? step : 1), step_dev, z, (const int*)skip_dev);
     MMVID_LAUNCH_CHECK("ema_update");
     return MMVID_OK;
+}
+
+extern "C" int mmvid_ema_update(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
+                                const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, void* stream) {
+    return ema_launch(ema, p, n, decay, warmup, step, step_dev, row_flags, table_lo, table_rows, rowlen, nullptr, stream);
+}
+
+extern "C" int mmvid_ema_update_guarded(float* ema, const float* p, int64_t n, float decay, int warmup, int step, const float* step_dev,
+                                        const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen,
+                                        const int32_t* skip_dev, void* stream) {
+    MMVID_REQUIRE(((uintptr_t)skip_dev & 3) == 0, "ema_update_guarded: skip_dev must be 4-byte aligned");
+    return ema_launch(ema, p, n, decay, warmup, step, step_dev, row_flags, table_lo, table_rows, rowlen, skip_dev, stream);
 }

@@ -7,6 +7,7 @@
 //                 p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
 //                 also refreshes the bf16 shadow copy the MFMA kernels read.
 #include "../../include/mmvid_hip.h"
+#include "../../include/mmvid_hip_ext.h"
 #include "common.h"
 
 namespace {
@@ -51,7 +52,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    bf16_t* __restrict__ shadow, long n, AdamArgs a,
                                                    const float* __restrict__ sqnorm,
                                                    const float* __restrict__ step_dev,
-                                                   const float* __restrict__ lr_dev, LazyRows z) {
+                                                   const float* __restrict__ lr_dev, LazyRows z,
+                                                   const int* __restrict__ skip) {
+    if (skip && *skip) return;  // non-finite guard (mmvid_step_guard): a kernel argument's load, the same in every lane -- a scalar branch
     if (lr_dev) a.lr = *lr_dev;  // learning rate kept on the device (mmvid_lr_schedule): a captured step follows the schedule
     if (step_dev) {  // step count kept on the device (whole-step graph replay): bias corrections computed here
         const float t = *step_dev;
@@ -208,10 +211,11 @@ extern "C" int mmvid_adam_step_lr(float* p, const float* g, float* m, float* v, 
                                 sqnorm, grad_scale, nullptr, 0, 0, 0, stream);
 }
 
-extern "C" int mmvid_adam_step_rows(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
-                                    const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
-                                    const float* step_dev, float max_norm, const float* sqnorm, float grad_scale,
-                                    const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, void* stream) {
+// mmvid_adam_step_rows (skip_dev NULL) and mmvid_adam_step_guarded: one set of checks, one kernel
+static int adam_launch(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, const float* lr_dev,
+                       float beta1, float beta2, float eps, float weight_decay, int step, const float* step_dev, float max_norm,
+                       const float* sqnorm, float grad_scale, const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen,
+                       const int32_t* skip_dev, void* stream) {
     MMVID_REQUIRE(p && g && m && v && n >= 0 && (step >= 1 || step_dev), "adam_step: bad arguments");
     MMVID_REQUIRE(!row_flags || weight_decay == 0.f, "adam_step: lazy rows are exact only without weight decay");
     LazyRows z;
@@ -225,8 +229,55 @@ extern "C" int mmvid_adam_step_rows(float* p, const float* g, float* m, float* v
     a.bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)(step >= 1 ? step : 1)));
     a.max_norm = max_norm, a.grad_scale = grad_scale;
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)shadow_bf16,
-                       (long)n, a, sqnorm, step_dev, lr_dev, z);
+                       (long)n, a, sqnorm, step_dev, lr_dev, z, (const int*)skip_dev);
     MMVID_LAUNCH_CHECK("adam_step");
+    return MMVID_OK;
+}
+
+extern "C" int mmvid_adam_step_rows(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
+                                    const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                                    const float* step_dev, float max_norm, const float* sqnorm, float grad_scale,
+                                    const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, void* stream) {
+    return adam_launch(p, g, m, v, shadow_bf16, n, lr, lr_dev, beta1, beta2, eps, weight_decay, step, step_dev, max_norm, sqnorm,
+                       grad_scale, row_flags, table_lo, table_rows, rowlen, nullptr, stream);
+}
+
+extern "C" int mmvid_adam_step_guarded(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
+                                       const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                                       const float* step_dev, float max_norm, const float* sqnorm, float grad_scale,
+                                       const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen,
+                                       const int32_t* skip_dev, void* stream) {
+    MMVID_REQUIRE(((uintptr_t)skip_dev & 3) == 0, "adam_step_guarded: skip_dev must be 4-byte aligned");
+    return adam_launch(p, g, m, v, shadow_bf16, n, lr, lr_dev, beta1, beta2, eps, weight_decay, step, step_dev, max_norm, sqnorm,
+                       grad_scale, row_flags, table_lo, table_rows, rowlen, skip_dev, stream);
+}
+
+// The verdict of the non-finite guard and its counters (include/mmvid_hip_ext.h states the rule; tests/guard_ref.py is the host
+// replica).  One thread, plain loads and stores: the kernels that follow on the stream read guard_i[0].
+__global__ void step_guard_kernel(const float* __restrict__ sqnorm, float grad_scale, float* __restrict__ step_dev,
+                                  int* __restrict__ guard_i, float* __restrict__ guard_f) {
+    const float sq = *sqnorm;
+    const int skip = (__float_as_uint(sq) & 0x7f800000u) == 0x7f800000u;  // inf or NaN: the exponent is all ones
+    const float norm = __fmul_rn(sqrtf(sq), grad_scale);                 // what adam_kernel clips on
+    guard_i[0] = skip;
+    guard_i[1] += skip;
+    guard_i[2] = skip ? guard_i[2] + 1 : 0;
+    guard_i[3] += 1;
+    guard_f[0] = norm;
+    if (!skip) {
+        guard_f[1] = norm;
+        *step_dev += 1.f;
+    }
+}
+
+extern "C" int mmvid_step_guard(const float* sqnorm, float grad_scale, float* step_dev, int32_t* guard_i, float* guard_f,
+                                void* stream) {
+    MMVID_REQUIRE(sqnorm && step_dev && guard_i && guard_f, "step_guard: sqnorm, step_dev, guard_i and guard_f must not be NULL");
+    MMVID_REQUIRE((((uintptr_t)sqnorm | (uintptr_t)step_dev | (uintptr_t)guard_i | (uintptr_t)guard_f) & 3) == 0,
+                  "step_guard: pointers must be 4-byte aligned");
+    hipLaunchKernelGGL(step_guard_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sqnorm, grad_scale, step_dev, (int*)guard_i,
+                       guard_f);
+    MMVID_LAUNCH_CHECK("step_guard");
     return MMVID_OK;
 }
 

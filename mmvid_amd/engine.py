@@ -63,8 +63,12 @@ def refuse_unproven_width(model, what):
 class FlatTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  process_group=None, bucket_mb=64, order=None, lr_schedule=None, force_exchange=False, sparse_tables=True,
-                 lazy_rows=True, exchange=None, ema_decay=None, ema_warmup=False):
+                 lazy_rows=True, exchange=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False):
         self.model = model
+        # non-finite guard (INTEGRATION.md "Non-finite guard"): False = off -- no buffer, the unguarded step's launches, state_dict() unchanged
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f'skip_nonfinite={skip_nonfinite!r}: True or False')
+        self.skip_nonfinite = skip_nonfinite
         # weight EMA (INTEGRATION.md "Weight EMA"): None = off -- no buffer, no launch, state_dict() unchanged key for key
         if ema_decay is not None:
             if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= float(ema_decay) < 1.0:  # (NaN, inf: False)
@@ -125,6 +129,11 @@ class FlatTrainer:
         # the right Adam bias corrections and learning rate without the host passing new scalars
         self._step_dev = torch.zeros(1, device=dev, dtype=torch.float32) if dev.type == 'cuda' else None
         self._lr_dev = torch.full((1, ), float(lr), device=dev, dtype=torch.float32) if dev.type == 'cuda' else None
+        # the guard's device state (mmvid_step_guard): guard_i = verdict, steps skipped, current run of skips, steps seen;
+        # guard_f = gradient norm of the last step, last finite gradient norm.  A host trainer has no optimiser kernel to guard.
+        guarded = self.skip_nonfinite and dev.type == 'cuda'
+        self.guard_i = torch.zeros(4, device=dev, dtype=torch.int32) if guarded else None
+        self.guard_f = torch.zeros(2, device=dev, dtype=torch.float32) if guarded else None
         self._comm_stream = torch.cuda.Stream(device=dev) if dev.type == 'cuda' else None
         self._works = []
         self._sent_from = tot  # gradients at flat offsets >= this are already on the wire this step
@@ -236,7 +245,9 @@ class FlatTrainer:
     def state_dict(self):
         """Optimiser state in torch.optim.Adam's layout (train.py:202-203, 352, 387 save / restore `optimizer`): per
         parameter exp_avg / exp_avg_sq / step, keyed by position in `self.names` order (recorded under 'names'), plus the
-        front-end's (seed, forward count) so a resumed run continues its mask / warp stream instead of replaying it."""
+        front-end's (seed, forward count) so a resumed run continues its mask / warp stream instead of replaying it.  With the
+        non-finite guard the step count is first reconciled with the device (guard_stats): 'step' is the number of APPLIED steps."""
+        guard = self.guard_stats() if self.guard_i is not None else None
         state = {}
         for i, (p, o) in enumerate(zip(self.params, self.offsets)):
             n = p.numel()
@@ -250,6 +261,8 @@ class FlatTrainer:
             out['frontend'] = fe.state_dict()
         if self.E is not None:
             out['ema'] = {'decay': self.ema_decay, 'warmup': self.ema_warmup, 'weights': self.ema_state_dict()}
+        if guard is not None:
+            out['guard'] = {'skipped': guard['skipped'], 'seen': guard['seen']}
         return out
 
     def load_state_dict(self, sd):
@@ -295,6 +308,10 @@ class FlatTrainer:
             self.step_count = steps.pop()
             if self._step_dev is not None:
                 self._step_dev.fill_(float(self.step_count))
+        if self.guard_i is not None:  # the two totals as saved (none saved: zero); the run of skips starts again
+            saved = sd.get('guard') or {}
+            self.guard_i.copy_(torch.tensor([0, int(saved.get('skipped', 0)), 0, int(saved.get('seen', 0))], dtype=torch.int32))
+            self.guard_f.zero_()
         g = sd['param_groups'][0]
         self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
         fe = getattr(self.model, 'frontend', None)
@@ -604,14 +621,37 @@ class FlatTrainer:
                 sc = self.lr_schedule
                 ops.lr_schedule(self._step_dev, 1, sc.min_lr, sc.max_lr, sc.warmup, sc.every, self._lr_dev)
                 lr_dev = self._lr_dev
-            ops.counter_add(self._step_dev, 1.0)
+            if self.guard_i is None:
+                ops.counter_add(self._step_dev, 1.0)
         ops.grad_sqnorm(self.G, self._sq, partials=self._sq_partials, lazy=self._lazy_arg())
+        skip = None
+        if self.guard_i is not None:
+            # the verdict on the exchanged gradient, on the device: step_guard advances the step count in counter_add's place (only
+            # where the step is applied) and Adam and the EMA return at once where it says skip -- no host input, so a replay obeys it
+            ops.step_guard(self._sq, gscale, self._step_dev, self.guard_i, self.guard_f)
+            skip = self.guard_i  # (element 0)
         ops.adam_step(self.P, self.G, self.M, self.V, self.S, self.step_count, self.lr, self.betas, self.eps, self.wd,
-                      self.max_norm, self._sq, gscale, step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg())
+                      self.max_norm, self._sq, gscale, step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg(), skip_dev=skip)
         if self.E is not None:  # same stream, after Adam; t is read from the device counter: a captured step carries it as it stands
-            ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, step_dev=self._step_dev, lazy=self._lazy_arg())
+            ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, step_dev=self._step_dev, lazy=self._lazy_arg(),
+                           skip_dev=skip)
         for w in self._attached:
-            w.mark_fresh()  # the Adam kernel wrote the attached bf16 views (a weight that is not attached is frozen: no kernel writes it)
+            # the Adam kernel wrote the attached bf16 views (a weight that is not attached is frozen: no kernel writes it); after a
+            # skipped step they still equal cast(P)
+            w.mark_fresh()
+
+    def guard_stats(self):
+        """The non-finite guard's counters, in one device read (it synchronises): 'seen' steps, of which 'skipped'; 'run', the current
+        run of skipped steps; 'last_skipped'; 'grad_norm' of the last step (sqrt(sum g^2) / world, before clipping; NaN or inf where it
+        was skipped) and 'last_finite_grad_norm'.  Sets `step_count` to the device's count of applied steps."""
+        if self.guard_i is None:
+            raise RuntimeError('this trainer has no non-finite guard (skip_nonfinite=False, or a host trainer)')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('guard_stats() inside a stream capture: it reads the device')
+        raw = torch.cat([self.guard_i, self.guard_f.view(torch.int32), self._step_dev.view(torch.int32)]).cpu()
+        i, f = raw[:4].tolist(), raw[4:].view(torch.float32).tolist()
+        self.step_count = int(f[2])
+        return {'seen': i[3], 'skipped': i[1], 'run': i[2], 'last_skipped': bool(i[0]), 'grad_norm': f[0], 'last_finite_grad_norm': f[1]}
 
     def grad_norm(self):
         return float(self.G.norm()) / self.world
@@ -694,6 +734,7 @@ class GraphedStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         saved = (trainer.step_count, trainer._step_dev.clone(), self._frontend_steps())
+        guard = None if trainer.guard_i is None else (trainer.guard_i.clone(), trainer.guard_f.clone())
         graph = torch.cuda.CUDAGraph()
         # with a process group alive, its watchdog thread polls events while we capture: only THIS thread's calls may be
         # policed (the default "global" mode turns the watchdog's hipEventQuery into a capture violation)
@@ -713,6 +754,9 @@ class GraphedStep:
         trainer.step_count = saved[0]
         trainer._step_dev.copy_(saved[1])
         self._frontend_steps(saved[2])
+        if guard is not None:
+            trainer.guard_i.copy_(guard[0])
+            trainer.guard_f.copy_(guard[1])
 
     def _frontend_steps(self, restore=None):
         fe = getattr(self.trainer.model, 'frontend', None)

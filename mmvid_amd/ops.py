@@ -474,25 +474,43 @@ def grad_sqnorm(g, out, partials=None, lazy=None):
 
 
 def adam_step(p, g, m, v, shadow, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=0.0,
-              sqnorm=None, grad_scale=1.0, step_dev=None, lr_dev=None, lazy=None):
+              sqnorm=None, grad_scale=1.0, step_dev=None, lr_dev=None, lazy=None, skip_dev=None):
+    """skip_dev: the verdict of step_guard (int32 on the device) -- where it is non-zero at execution the kernel writes nothing
+    (mmvid_adam_step_guarded).  None: the unguarded entry, as ever."""
     for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
         _chk(t, f32, n)
     fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
-    call('mmvid_adam_step_rows', _p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), float(lr), _p(lr_dev), float(betas[0]),
-         float(betas[1]), float(eps), float(weight_decay), int(step), _p(step_dev), float(max_norm), _p(sqnorm),
-         float(grad_scale), _p(fl), int(lo), int(rows), int(rowlen), _stream())
+    args = (_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), float(lr), _p(lr_dev), float(betas[0]), float(betas[1]), float(eps),
+            float(weight_decay), int(step), _p(step_dev), float(max_norm), _p(sqnorm), float(grad_scale), _p(fl), int(lo), int(rows),
+            int(rowlen))
+    if skip_dev is None:
+        call('mmvid_adam_step_rows', *args, _stream())
+    else:
+        call('mmvid_adam_step_guarded', *args, _p(_chk(skip_dev, torch.int32, 'skip_dev')), _stream())
 
 
-def ema_update(ema, p, decay, warmup, step, step_dev=None, lazy=None):
+def ema_update(ema, p, decay, warmup, step, step_dev=None, lazy=None, skip_dev=None):
     """ema <- fmaf(1 - d, p - ema, ema) over the flat fp32 buffers, d = decay or (warmup) min(decay, (1 + t) / (10 + t)) with t the
     count of finished steps (`step`, or the device scalar step_dev); lazy as in adam_step: unflagged rows are not touched
-    (include/mmvid_hip_ext.h: mmvid_ema_update)."""
+    (include/mmvid_hip_ext.h: mmvid_ema_update).  skip_dev as in adam_step (mmvid_ema_update_guarded)."""
     _chk(ema, f32, 'ema'), _chk(p, f32, 'p')
     if ema.numel() != p.numel():
         raise ValueError(f'ema_update: ema has {ema.numel()} elements, p {p.numel()}')
     fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
-    call('mmvid_ema_update', _p(ema), _p(p), p.numel(), float(decay), int(bool(warmup)), int(step), _p(step_dev), _p(fl), int(lo),
-         int(rows), int(rowlen), _stream())
+    args = (_p(ema), _p(p), p.numel(), float(decay), int(bool(warmup)), int(step), _p(step_dev), _p(fl), int(lo), int(rows), int(rowlen))
+    if skip_dev is None:
+        call('mmvid_ema_update', *args, _stream())
+    else:
+        call('mmvid_ema_update_guarded', *args, _p(_chk(skip_dev, torch.int32, 'skip_dev')), _stream())
+
+
+def step_guard(sqnorm, grad_scale, step_dev, guard_i, guard_f):
+    """The non-finite guard's verdict on the device (include/mmvid_hip_ext.h: mmvid_step_guard): guard_i (int32 [4]) = skip, skipped,
+    run, seen; guard_f (fp32 [2]) = gradient norm, last finite gradient norm; step_dev advances only where the step is applied."""
+    _chk(sqnorm, f32, 'sqnorm'), _chk(step_dev, f32, 'step_dev'), _chk(guard_f, f32, 'guard_f'), _chk(guard_i, torch.int32, 'guard_i')
+    if guard_i.numel() != 4 or guard_f.numel() != 2 or sqnorm.numel() < 1 or step_dev.numel() < 1:
+        raise ValueError('step_guard: guard_i holds 4 int32, guard_f 2 fp32, sqnorm and step_dev one fp32 each')
+    call('mmvid_step_guard', _p(sqnorm), float(grad_scale), _p(step_dev), _p(guard_i), _p(guard_f), _stream())
 
 
 def lr_schedule(step_dev, kind, lr_min, lr_max, warmup, every, lr_out):
