@@ -92,6 +92,40 @@ int mmvid_ema_update_guarded(float* ema, const float* p, int64_t n, float decay,
                              const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, const int32_t* skip_dev,
                              void* stream);
 
+/* ---- Per-video sampling parameters: top-k, top-p and the softmax temperature of a row read on the device ---------------------------
+ *
+ * Serves the truncation of both samplers (mmvid_logits_truncate in mmvid_hip.h states the rule and which reference lines it stands
+ * for: the draw of dalle_bert.py:527-534, the top_k filter of dalle_artv.py:61-67 and the division by the temperature of :274-276)
+ * for a batch whose videos do not share their settings.  The contract is mmvid_logits_truncate's -- the same rule, one wave per row,
+ * the row in registers, 1 <= V <= 2048, the guided form with logits_u / scale_dev / rows_per_scale, kept nullable -- and with
+ * top_k_dev, top_p_dev and inv_div_dev all NULL and divide_out 0 the output is that entry's, byte for byte.
+ *
+ * Per-row arrays.  top_k_dev (int32), top_p_dev (fp32) and inv_div_dev (fp32) live on the device, hold R / rows_per_param entries
+ * each and are read at execution, entry r / rows_per_param for row r (a captured step may change them between replays).  Each is
+ * optional: NULL means the scalar argument (top_k, top_p, 1.0f / logit_div) holds for every row.  inv_div_dev holds 1 / temperature
+ * as the host rounds it in fp32 -- the 1.0f / logit_div that the C entries compute; the device never divides.
+ *
+ * Device values.  A top_k outside [1, V) switches top-k off for its row (0 is the documented "off"); a top_p >= 1 switches the
+ * nucleus off.  A top_p that is not > 0, or an inv_div that is not finite and positive, leaves the values of THAT ROW unspecified:
+ * no other row, no byte outside out [R, V] and kept [R] and no trip count depends on it.  The caller checks its values on the host
+ * (mmvid_amd/sampling.py: check_video_params).
+ *
+ * divide_out.  0: a kept class is written as g, as mmvid_logits_truncate writes it.  1: as g * inv_div of its row, one rounded fp32
+ * product -- the product a race forms from g and 1.0f / logit_div -- so mmvid_sample_race* on out with logit_div = 1 draws what it
+ * would draw on the undivided row with that row's logit_div: this is how a per-row temperature reaches a draw kernel that takes one
+ * scalar.  A row with both filters off is copied through (divide_out 0) or divided (1).  kept counts the finite values written.
+ *
+ * No atomics, no LDS, no barrier; a row's stores follow all of its loads, so out may be logits.
+ *
+ * Refused with an error (never a fault, nothing launched, nothing written): everything mmvid_logits_truncate refuses (NULL logits
+ * or out; V outside [1, 2048]; R < 0; ld or ld_out below V; logit_div or the scalar top_p not > 0; logits_u without scale_dev or the
+ * reverse; in the guided form rows_per_scale <= 0 or R no multiple of it); rows_per_param <= 0 or R no multiple of it; a per-row
+ * array that is not 4-byte aligned; divide_out outside {0, 1}.  R == 0: nothing is launched. */
+int mmvid_logits_truncate_rows(const float* logits, const float* logits_u, int64_t ld, const float* scale_dev, int64_t rows_per_scale,
+                               float logit_div, int top_k, float top_p, const int32_t* top_k_dev, const float* top_p_dev,
+                               const float* inv_div_dev, int64_t rows_per_param, int divide_out, int64_t R, int V,
+                               float* out, int64_t ld_out, int32_t* kept, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,7 +83,8 @@ def complete_seeded(model, text, frames, given, seeds, *, visual=None, mask_pred
     mode whose indices are exact.  `given`: see token_mask; every video may have its own.  `text`, `visual`, `erase_visual`,
     `vc_mode`, `face_mode`, `mask_predict_steps`, `mp_config`, `dynamic`, `guidance_scale`, `guidance_drop`, `negative_text`, `top_k`, `top_p`: as for
     generate_images (guided completion: the given tokens are visible to both branches, and belong to the conditional one).  `seeds`:
-    one per video, as for BERT.mask_predict (not with erase_visual); None: the unseeded call, which is `complete`.
+    one per video, as for BERT.mask_predict (not with erase_visual); None: the unseeded call, which is `complete`.  The per-video
+    `video_top_k` / `video_top_p` of BERT.mask_predict are not taken here (`complete`'s signature is pinned): call the sampler.
 
     One host read precedes the sampler's loop: the number of known tokens per video together with the count of given token ids
     outside [0, num_image_tokens), which raises ValueError.  `decode` decodes the result once, in slices of `vae._max_frames`;
@@ -147,7 +148,8 @@ def complete_seeded(model, text, frames, given, seeds, *, visual=None, mask_pred
 @torch.no_grad()
 def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, temperature=1., erase_visual=False, vc_mode=None,
                   face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None, guidance_drop=sampling.GUIDANCE_DROPS,
-                  negative_text=None, paste=True, seeds=None, _race=None, _trace=None):
+                  negative_text=None, paste=True, seeds=None, video_top_k=None, video_top_p=None, video_temperature=None, _race=None,
+                  _trace=None):
     """Video prediction on the autoregressive (ART-V) model -> (frames_u8 [b, T, H, W, 3] uint8 on the device, tokens [b, T * n] int64).
 
     `frames`: as for `complete` (fp32 [b, T, 3, H, W] in [0, 1], uint8 [b, T, H, W, 3], or int64 tokens [b, T * n]); only the frames
@@ -157,13 +159,15 @@ def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, 
     do not see it -- [0, 1, 1, 0] generates frame 0 from the text and the visual control alone, then frame 3 from frames 0-2 -- so
     in-betweening key frames is the BERT's task (`complete`), and prediction from the first frames is this one's.
 
-    The other keywords (`seeds` among them) are those of DALLE.generate_images, which samples (`given=(mask, tokens)`).  The result is decoded once, in
+    The other keywords (`seeds` and the per-video `video_top_k`, `video_top_p`, `video_temperature` among them) are those of DALLE.generate_images, which samples (`given=(mask, tokens)`).  The result is decoded once, in
     slices of `vae._max_frames`; with `paste` and pixel `frames` the known frames are the input's own bytes and not their VQGAN
     reconstruction (csrc/frames.hip); with token input there are no pixels to paste and the plain byte kernel runs."""
     T, n, s, f = model.num_targets, model.image_seq_len, model.image_size, model.image_fmap_size
     b, dev = text.shape[0], text.device
     mask = artv_sampling.check_frame_mask(given, b, T)  # (before the frames are tokenised)
     seeds = seeded.check_seeds(seeds, b, race=_race, erase_visual=erase_visual)
+    sampling.check_video_params(video_top_k, video_top_p, video_temperature, b, model.num_image_tokens, None, top_k, top_p,
+                                temperature)  # (before the frames are tokenised)
     if isinstance(visual, (list, tuple)):  # frames [b, 3, H, W] each, as get_image_tokens takes them
         visual = torch.stack(list(visual), dim=1) if len(visual) else None
     was_training = model.training
@@ -173,7 +177,8 @@ def complete_artv(model, text, frames, given, *, visual=None, filter_thres=0.5, 
         _, seq = model.sample_tokens(text, visual=visual, filter_thres=filter_thres, temperature=temperature, erase_visual=erase_visual,
                                      vc_mode=vc_mode, face_mode=face_mode, use_cache=use_cache, top_k=top_k, top_p=top_p,
                                      guidance_scale=guidance_scale, guidance_drop=guidance_drop, negative_text=negative_text,
-                                     given=(mask, tokens.to(dev)), seeds=seeds, _race=_race, _trace=_trace)
+                                     given=(mask, tokens.to(dev)), seeds=seeds, video_top_k=video_top_k, video_top_p=video_top_p,
+                                     video_temperature=video_temperature, _race=_race, _trace=_trace)
         flat = seq.reshape(b * T, n)
         out = torch.empty(b * T, s, s, 3, device=dev, dtype=torch.uint8)
         grid = mask.to(dev).view(b * T, 1, 1).expand(b * T, f, f).contiguous()

@@ -19,8 +19,11 @@
 //                                                          head of the order whose mass reaches top_p
 // With both on a class must pass both.  out = g where kept (not divided), -inf elsewhere; kept[r] = number of finite outputs.  So
 // sample_race(out, E, noise_u, temperature, logit_div) is the truncated draw, its y the probability under the truncated distribution,
-// and noise never brings an excluded class back.
+// and noise never brings an excluded class back.  logits_truncate_rows_kernel is the same rule with top_k, top_p and 1 / logit_div of a
+// row read on the device (per-video sampling parameters); it can write the kept values divided, g * (1 / logit_div), for a race with
+// logit_div = 1.
 #include "../../include/mmvid_hip.h"
+#include "../../include/mmvid_hip_ext.h"
 #include "common.h"
 
 namespace {
@@ -238,32 +241,12 @@ __device__ __forceinline__ uint32_t order_key(float v) {
 }
 __device__ __forceinline__ float first_lane(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
-template <int NS, bool GUIDED>
-__global__ __launch_bounds__(256) void logits_truncate_kernel(const float* logits, const float* logits_u, long ld,
-                                                              const float* __restrict__ scale_dev, long rows_per_scale, float inv_div,
-                                                              int top_k, float top_p, long R, int V, float* out, long ld_out,
-                                                              int* __restrict__ kept) {
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const float* x = logits + r * ld;
-    const float* xu = GUIDED ? logits_u + r * ld : nullptr;
-    const float w = GUIDED ? scale_dev[r / rows_per_scale] : 0.f;
-    float g[NS], p[NS];
-    uint32_t key[NS];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int c = lane + 64 * i;
-        const bool on = c < V;
-        g[i] = on ? (GUIDED ? guided_logit(x[c], xu[c], w) : x[c]) : -INFINITY;
-        key[i] = on ? order_key(g[i]) : 0u;  // below the key of every value, -inf included: a slot past V is never counted
-        mx = fmaxf(mx, g[i] * inv_div);
-    }
-    mx = wave_max(mx);
-#pragma unroll
-    for (int i = 0; i < NS; ++i) p[i] = mx == -INFINITY ? 0.f : expf(g[i] * inv_div - mx);  // (a row of -inf has no mass; a slot past V: expf(-inf))
+// The two searches and the admission at the edge key, on a row that its wave holds as (key, p) per slot: bit i of the result says that
+// slot i stays.  top_k, top_p and V are wave-uniform.  Shared by the scalar kernel and the per-row one, so a row's kept set is one
+// function of (g, inv_div, top_k, top_p) whichever of the two computes it.
+template <int NS>
+__device__ __forceinline__ uint32_t truncate_keep(const uint32_t (&key)[NS], const float (&p)[NS], int top_k, float top_p, int V,
+                                                  unsigned long long below) {
     uint32_t keep = 0xffffffffu;  // bit i: slot i stays
     if (top_k >= 1 && top_k < V) {
         uint32_t T = 0;
@@ -317,6 +300,36 @@ __global__ __launch_bounds__(256) void logits_truncate_kernel(const float* logit
             if (!(key[i] > T || (at && m_above + (float)j * p[i] < theta))) keep &= ~(1u << i);
         }
     }
+    return keep;
+}
+
+template <int NS, bool GUIDED>
+__global__ __launch_bounds__(256) void logits_truncate_kernel(const float* logits, const float* logits_u, long ld,
+                                                              const float* __restrict__ scale_dev, long rows_per_scale, float inv_div,
+                                                              int top_k, float top_p, long R, int V, float* out, long ld_out,
+                                                              int* __restrict__ kept) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const float* x = logits + r * ld;
+    const float* xu = GUIDED ? logits_u + r * ld : nullptr;
+    const float w = GUIDED ? scale_dev[r / rows_per_scale] : 0.f;
+    float g[NS], p[NS];
+    uint32_t key[NS];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int c = lane + 64 * i;
+        const bool on = c < V;
+        g[i] = on ? (GUIDED ? guided_logit(x[c], xu[c], w) : x[c]) : -INFINITY;
+        key[i] = on ? order_key(g[i]) : 0u;  // below the key of every value, -inf included: a slot past V is never counted
+        mx = fmaxf(mx, g[i] * inv_div);
+    }
+    mx = wave_max(mx);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) p[i] = mx == -INFINITY ? 0.f : expf(g[i] * inv_div - mx);  // (a row of -inf has no mass; a slot past V: expf(-inf))
+    const uint32_t keep = truncate_keep<NS>(key, p, top_k, top_p, V, below);  // bit i: slot i stays
     float* o = out + r * ld_out;
     int n_kept = 0;
 #pragma unroll
@@ -325,6 +338,59 @@ __global__ __launch_bounds__(256) void logits_truncate_kernel(const float* logit
         const bool k = c < V && ((keep >> i) & 1u);
         if (c < V) o[c] = k ? g[i] : -INFINITY;
         n_kept += __popcll(__ballot(k && fabsf(g[i]) < INFINITY));
+    }
+    if (kept && lane == 0) kept[r] = n_kept;
+}
+
+// logits_truncate_kernel with the filter settings of row r read on the device: top_k_dev, top_p_dev and inv_div_dev (each nullable:
+// the scalar argument holds for every row) at [r / rows_per_param], one load each, made wave-uniform so that the searches branch and
+// count as they do on launch scalars.  The row's g, P and kept set are the scalar kernel's on (top_k, top_p, inv_div) of that row: the
+// same expressions and the same truncate_keep.  divide_out: a kept class is written as g * inv_div, the one rounded product that a race
+// forms from g and 1 / logit_div, so the race that follows runs with logit_div = 1 (x * 1.f is x) on the same keys.  A device value
+// outside the documented range only changes which classes of its own row stay: every trip count and every address is independent of it.
+template <int NS, bool GUIDED>
+__global__ __launch_bounds__(256) void logits_truncate_rows_kernel(const float* logits, const float* logits_u, long ld,
+                                                                   const float* __restrict__ scale_dev, long rows_per_scale,
+                                                                   float inv_div, int top_k, float top_p,
+                                                                   const int* __restrict__ top_k_dev, const float* __restrict__ top_p_dev,
+                                                                   const float* __restrict__ inv_div_dev, long rows_per_param,
+                                                                   int divide_out, long R, int V, float* out, long ld_out,
+                                                                   int* __restrict__ kept) {
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const long q = r / rows_per_param;
+    if (top_k_dev) top_k = __builtin_amdgcn_readfirstlane(top_k_dev[q]);
+    if (top_p_dev) top_p = first_lane(top_p_dev[q]);
+    if (inv_div_dev) inv_div = first_lane(inv_div_dev[q]);
+    const float* x = logits + r * ld;
+    const float* xu = GUIDED ? logits_u + r * ld : nullptr;
+    const float w = GUIDED ? scale_dev[r / rows_per_scale] : 0.f;
+    float g[NS], p[NS];
+    uint32_t key[NS];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int c = lane + 64 * i;
+        const bool on = c < V;
+        g[i] = on ? (GUIDED ? guided_logit(x[c], xu[c], w) : x[c]) : -INFINITY;
+        key[i] = on ? order_key(g[i]) : 0u;
+        mx = fmaxf(mx, g[i] * inv_div);
+    }
+    mx = wave_max(mx);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) p[i] = mx == -INFINITY ? 0.f : expf(g[i] * inv_div - mx);
+    const uint32_t keep = truncate_keep<NS>(key, p, top_k, top_p, V, below);
+    float* o = out + r * ld_out;
+    int n_kept = 0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int c = lane + 64 * i;
+        const bool k = c < V && ((keep >> i) & 1u);
+        const float v = divide_out ? g[i] * inv_div : g[i];
+        if (c < V) o[c] = k ? v : -INFINITY;
+        n_kept += __popcll(__ballot(k && fabsf(v) < INFINITY));
     }
     if (kept && lane == 0) kept[r] = n_kept;
 }
@@ -777,6 +843,57 @@ extern "C" int mmvid_logits_truncate(const float* logits, const float* logits_u,
         launch_logits_truncate<false>(logits, nullptr, (long)ld, nullptr, 1L, 1.0f / logit_div, top_k, top_p, (long)R, V, out, (long)ld_out,
                                       (int*)kept, (hipStream_t)stream);
     MMVID_LAUNCH_CHECK("logits_truncate");
+    return MMVID_OK;
+}
+
+// mmvid_logits_truncate with per-row filter settings read on the device (include/mmvid_hip_ext.h): top_k_dev / top_p_dev / inv_div_dev
+// [R / rows_per_param], each nullable (the scalar holds).  Every refusal comes before the launch.
+template <bool GUIDED>
+static void launch_logits_truncate_rows(const float* logits, const float* logits_u, long ld, const float* scale_dev, long rows_per_scale,
+                                        float inv_div, int top_k, float top_p, const int* top_k_dev, const float* top_p_dev,
+                                        const float* inv_div_dev, long rows_per_param, int divide_out, long R, int V, float* out,
+                                        long ld_out, int* kept, hipStream_t stream) {
+    const dim3 grid(cdiv(R, 4)), block(256);
+    if (V <= 256)
+        hipLaunchKernelGGL((logits_truncate_rows_kernel<4, GUIDED>), grid, block, 0, stream, logits, logits_u, ld, scale_dev, rows_per_scale,
+                           inv_div, top_k, top_p, top_k_dev, top_p_dev, inv_div_dev, rows_per_param, divide_out, R, V, out, ld_out, kept);
+    else if (V <= 1024)
+        hipLaunchKernelGGL((logits_truncate_rows_kernel<16, GUIDED>), grid, block, 0, stream, logits, logits_u, ld, scale_dev, rows_per_scale,
+                           inv_div, top_k, top_p, top_k_dev, top_p_dev, inv_div_dev, rows_per_param, divide_out, R, V, out, ld_out, kept);
+    else
+        hipLaunchKernelGGL((logits_truncate_rows_kernel<32, GUIDED>), grid, block, 0, stream, logits, logits_u, ld, scale_dev, rows_per_scale,
+                           inv_div, top_k, top_p, top_k_dev, top_p_dev, inv_div_dev, rows_per_param, divide_out, R, V, out, ld_out, kept);
+}
+
+extern "C" int mmvid_logits_truncate_rows(const float* logits, const float* logits_u, int64_t ld, const float* scale_dev,
+                                          int64_t rows_per_scale, float logit_div, int top_k, float top_p, const int32_t* top_k_dev,
+                                          const float* top_p_dev, const float* inv_div_dev, int64_t rows_per_param, int divide_out,
+                                          int64_t R, int V, float* out, int64_t ld_out, int32_t* kept, void* stream) {
+    MMVID_REQUIRE(logits && out, "logits_truncate_rows: null logits or out");
+    MMVID_REQUIRE(V >= 1 && V <= 2048, "logits_truncate_rows: V=%d is outside [1, 2048] (a wave holds its row in registers)", V);
+    MMVID_REQUIRE(R >= 0 && ld >= V && ld_out >= V, "logits_truncate_rows: R=%ld ld=%ld ld_out=%ld V=%d", (long)R, (long)ld, (long)ld_out, V);
+    MMVID_REQUIRE(logit_div > 0.f, "logits_truncate_rows: logit_div (the softmax temperature divisor) must be > 0");
+    MMVID_REQUIRE(top_p > 0.f, "logits_truncate_rows: top_p must be > 0 (>= 1 switches the nucleus off)");  // (false for NaN too)
+    MMVID_REQUIRE((logits_u != nullptr) == (scale_dev != nullptr),
+                  "logits_truncate_rows: logits_u and scale_dev come together (the guided form)");
+    if (logits_u)
+        MMVID_REQUIRE(rows_per_scale > 0 && R % rows_per_scale == 0, "logits_truncate_rows: R=%ld is no multiple of rows_per_scale=%ld",
+                      (long)R, (long)rows_per_scale);
+    MMVID_REQUIRE(rows_per_param > 0 && R % rows_per_param == 0, "logits_truncate_rows: R=%ld is no multiple of rows_per_param=%ld", (long)R,
+                  (long)rows_per_param);
+    MMVID_REQUIRE((((uintptr_t)top_k_dev | (uintptr_t)top_p_dev | (uintptr_t)inv_div_dev) & 3) == 0,
+                  "logits_truncate_rows: a per-row array is not 4-byte aligned");
+    MMVID_REQUIRE(divide_out == 0 || divide_out == 1, "logits_truncate_rows: divide_out=%d is neither 0 nor 1", divide_out);
+    if (R == 0) return MMVID_OK;
+    if (logits_u)
+        launch_logits_truncate_rows<true>(logits, logits_u, (long)ld, scale_dev, (long)rows_per_scale, 1.0f / logit_div, top_k, top_p,
+                                          (const int*)top_k_dev, top_p_dev, inv_div_dev, (long)rows_per_param, divide_out, (long)R, V, out,
+                                          (long)ld_out, (int*)kept, (hipStream_t)stream);
+    else
+        launch_logits_truncate_rows<false>(logits, nullptr, (long)ld, nullptr, 1L, 1.0f / logit_div, top_k, top_p, (const int*)top_k_dev,
+                                           top_p_dev, inv_div_dev, (long)rows_per_param, divide_out, (long)R, V, out, (long)ld_out,
+                                           (int*)kept, (hipStream_t)stream);
+    MMVID_LAUNCH_CHECK("logits_truncate_rows");
     return MMVID_OK;
 }
 

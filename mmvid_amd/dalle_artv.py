@@ -285,6 +285,18 @@ class DALLE(nn.Module):
 
     _scale_vector = staticmethod(sampling.scale_vector)
 
+    @staticmethod
+    def _video_trunc(B, V, device, top_k, top_p, temperature, video_top_k, video_top_p, video_temperature):
+        """The `trunc` of a call's draws (token_draw): check_truncation_artv's scalar pair or None without the per-video keywords; with one
+        of them a token_draw.RowParams over vectors [B] built here, once per call, after every value was checked on the host -- the
+        captured step reads them through pointers that stay.  Such a call always runs the per-row launch, whatever the values."""
+        video = sampling.check_video_params(video_top_k, video_top_p, video_temperature, B, V, None, top_k, top_p, temperature)
+        pair = sampling.check_truncation_artv(top_k, top_p, V)
+        if video is None:
+            return pair
+        k, p = pair or (None, None)
+        return token_draw.RowParams(1, *video.device(device), top_k=k, top_p=p)
+
     def _draw(self, block_logits, filter_thres, temperature, race, name, trunc=None, logits_u=None, scale=None):
         """One token per row from the logits of the position's class block (dalle_artv.py:274-276): top_k over ALL total_tokens classes keeps
         k = int((1 - thres) * total_tokens) of them; the classes outside the block sit at -max, so the filter only ever removes block classes
@@ -296,11 +308,14 @@ class DALLE(nn.Module):
         return token_draw.draw(block_logits, E, logits_u=logits_u, scale=scale, rows_per_scale=1, trunc=trunc, logit_div=temperature,
                                want_y=False)[0].view(B, 1)
 
-    def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None, logits_u=None, guidance_scale=None):
+    def sampling_probs(self, block_logits, filter_thres=0.5, temperature=1.0, top_k=None, top_p=None, logits_u=None, guidance_scale=None,
+                       video_top_k=None, video_top_p=None, video_temperature=None):
         """The probability vector `_draw` samples from (tests compare it with the reference's full-width expression); with logits_u and
-        guidance_scale, of the guided, then truncated, value (both filters off: the guided value is copied through)."""
+        guidance_scale, of the guided, then truncated, value (both filters off: the guided value is copied through).  video_top_k,
+        video_top_p, video_temperature: one value per row (_video_trunc); the value is then divided already where temperatures are given."""
         B, guide = block_logits.shape[0], {}
-        trunc = sampling.check_truncation_artv(top_k, top_p, block_logits.shape[1])
+        trunc = self._video_trunc(B, block_logits.shape[1], block_logits.device, top_k, top_p, temperature, video_top_k, video_top_p,
+                                  video_temperature)
         if (logits_u is None) != (guidance_scale is None):
             raise ValueError('sampling_probs: logits_u and guidance_scale come together')
         if logits_u is not None:
@@ -309,13 +324,14 @@ class DALLE(nn.Module):
         else:
             block_logits = keep_top(block_logits, k_keep(filter_thres, self.total_tokens))
         lg = token_draw.race_value(block_logits.contiguous(), trunc=trunc, logit_div=temperature, materialise=True, **guide)[0]
-        return F.softmax(lg / temperature, dim=-1)
+        return F.softmax(lg / token_draw.race_div(trunc, temperature), dim=-1)
 
     @torch.no_grad()
     @eval_decorator
     def generate_images(self, text, *, clip=None, visual=None, mask=None, filter_thres=0.5, temperature=1.,
                         erase_visual=False, vc_mode=None, face_mode=None, use_cache=True, top_k=None, top_p=None, guidance_scale=None,
-                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, given=None, seeds=None, _race=None, _trace=None, **kwargs):
+                        guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None, given=None, seeds=None, video_top_k=None, video_top_p=None,
+                        video_temperature=None, _race=None, _trace=None, **kwargs):
         """dalle_artv.py:236-304.  use_cache=True (default): the prompt runs once and every sampled token costs one
         incremental step over the per-layer key/value cache; use_cache=False: the reference's algorithm (the whole
         transformer over the growing prefix per token).  Both draw from the same distribution: softmax over the image
@@ -342,11 +358,20 @@ class DALLE(nn.Module):
 
         `seeds` (a sequence or integer tensor of B values in [0, 2^63), one per video; guided: still one per video): every token race
         draws variates that are a function of the video's seed and the token's index in the target sequence (mmvid_amd/seeded.py), not of
-        torch's generator, the row or the batch; several masks in one batch are fine.  Refused with `_race` and with erase_visual."""
+        torch's generator, the row or the batch; several masks in one batch are fine.  Refused with `_race` and with erase_visual.
+
+        `video_top_k`, `video_top_p`, `video_temperature` (a sequence or tensor of B entries each; sampling.check_video_params): top_k,
+        top_p and temperature per video, so that requests with different settings share one batch.  0 / 1.0 / None entries switch a
+        filter off for their video; video_temperature replaces `temperature` (which stays 1).  The vectors live on the device for the
+        call and ONE ops.logits_truncate_rows per token reads them (it also divides by the video's temperature, and the race then
+        divides by 1): the call takes the separate launches at every batch size, captured as usual.  Under `given`, every group of
+        rows takes the entries of its rows.  No per-token schedule."""
         return self._decode_tokens(*self.sample_tokens(text, visual=visual, filter_thres=filter_thres, temperature=temperature,
                                                        erase_visual=erase_visual, vc_mode=vc_mode, face_mode=face_mode, use_cache=use_cache,
                                                        top_k=top_k, top_p=top_p, guidance_scale=guidance_scale, guidance_drop=guidance_drop,
-                                                       negative_text=negative_text, given=given, seeds=seeds, _race=_race, _trace=_trace), clip)
+                                                       negative_text=negative_text, given=given, seeds=seeds, video_top_k=video_top_k,
+                                                       video_top_p=video_top_p, video_temperature=video_temperature, _race=_race,
+                                                       _trace=_trace), clip)
 
     def _decode_tokens(self, text, tokens, clip=None):
         """The tail of generate_images: tokens [B, target_seq_len] -> (images, [], None), or (images, clip scores)."""
@@ -362,7 +387,8 @@ class DALLE(nn.Module):
     @eval_decorator
     def sample_tokens(self, text, *, visual=None, filter_thres=0.5, temperature=1., erase_visual=False, vc_mode=None, face_mode=None,
                       use_cache=True, top_k=None, top_p=None, guidance_scale=None, guidance_drop=sampling.GUIDANCE_DROPS, negative_text=None,
-                      given=None, seeds=None, _race=None, _trace=None, _substream=None):
+                      given=None, seeds=None, video_top_k=None, video_top_p=None, video_temperature=None, _race=None, _trace=None,
+                      _substream=None):
         """The sampler of generate_images without the decode -> (text [B, text_seq_len], tokens int64 [B, target_seq_len]).
         `_substream` (one int per video, with `seeds`): the window of a long video (long_video.window_substream)."""
         tsl = self.text_seq_len
@@ -378,7 +404,7 @@ class DALLE(nn.Module):
             if not gmask.any():  # nothing known: the call without `given`
                 groups = None
         guide = self._guidance(B, guidance_scale, guidance_drop, negative_text, filter_thres)
-        trunc = sampling.check_truncation_artv(top_k, top_p, self.num_image_tokens)
+        trunc = self._video_trunc(B, self.num_image_tokens, text.device, top_k, top_p, temperature, video_top_k, video_top_p, video_temperature)
         if _trace is not None and not use_cache:
             raise ValueError('_trace records the token loop over the key/value cache: use_cache=True')
         if groups is not None and all(all(p) for p, _ in groups):  # everything known: no tower work
@@ -407,7 +433,8 @@ class DALLE(nn.Module):
                 sel = idx if guide is None else torch.cat((idx, idx + B))
                 t, v, g = text.index_select(0, sel), (vis_tok.index_select(0, sel) if vis_tok is not None else None), gtok.index_select(0, idx)
                 s = scale.index_select(0, idx).contiguous() if scale is not None else None
-            parts.append((rows, self._sample_rows(t, v, len(rows), pattern, g, filter_thres, temperature, use_cache, trunc, s, _race, _trace,
+            tr = trunc.rows(idx) if isinstance(trunc, token_draw.RowParams) and len(groups) > 1 else trunc
+            parts.append((rows, self._sample_rows(t, v, len(rows), pattern, g, filter_thres, temperature, use_cache, tr, s, _race, _trace,
                                                   race if race is None or len(groups) == 1 else race.rows(rows))))
         return text_c, artv_sampling.scatter_rows(parts, B)
 

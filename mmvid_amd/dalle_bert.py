@@ -567,12 +567,15 @@ class BERT(nn.Module):
     def generate_images(self, text, *, visual=None, mask=None, img=None, argmax=False, dynamic=True, debug=False,
                         erase_visual=False, mask_predict_steps=10, preserve=None, t_overlap=1, pc_mode=None,
                         vc_mode=None, face_mode=None, mp_config=None, long_mode='long', guidance_scale=None,
-                        guidance_drop=('text', 'visual'), negative_text=None, top_k=None, top_p=None, seeds=None, **kwargs):
+                        guidance_drop=('text', 'visual'), negative_text=None, top_k=None, top_p=None, seeds=None, video_top_k=None,
+                        video_top_p=None, video_temperature=None, **kwargs):
         """dalle_bert.py:434-487 -> (images [b,T,3,H,W], pnag_samples, img_seq [(b T), n]).  `guidance_scale` (a float, one per step,
         one per video or [steps, b]: sampling.guidance_table) switches classifier-free guidance on; see guidance_control for
         `guidance_drop` and `negative_text`.  `top_k` / `top_p` (an int / a float, or one per step: sampling.check_truncation) draw
         every token from the k most likely classes / from the nucleus of mass top_p (of the guided distribution when guided).  `seeds` (a
-        sequence or integer tensor of b values in [0, 2^63), one per video): see mask_predict."""
+        sequence or integer tensor of b values in [0, 2^63), one per video): see mask_predict.  `video_top_k` / `video_top_p` (b values, or
+        [steps, b]: sampling.check_video_params): top_k / top_p per video, so that videos with different settings share one batch;
+        `video_temperature` is refused (the sampler has no softmax temperature)."""
         if seeded.check_seeds(seeds, text.shape[0], race=kwargs.get('_race'), erase_visual=erase_visual) is not None:
             kwargs.update(seeds=seeds)
         drop = sampling.check_guidance(self.num_visuals, self.fixed_language_model is not None, guidance_scale, guidance_drop,
@@ -581,6 +584,10 @@ class BERT(nn.Module):
             Tmax = (mp_config or {}).get('T', 0) if mask_predict_steps <= 0 else mask_predict_steps
             sampling.check_truncation(top_k, top_p, Tmax, self.num_image_tokens)
             kwargs.update(top_k=top_k, top_p=top_p)
+        if video_top_k is not None or video_top_p is not None or video_temperature is not None:
+            Tmax = (mp_config or {}).get('T', 0) if mask_predict_steps <= 0 else mask_predict_steps
+            sampling.check_video_params(video_top_k, video_top_p, video_temperature, text.shape[0], self.num_image_tokens, Tmax, top_k, top_p)
+            kwargs.update(video_top_k=video_top_k, video_top_p=video_top_p)
         control_emb = self(text, visual=visual, erase_visual=erase_visual, erase_visual_half=True, vc_mode=vc_mode,
                            face_mode=face_mode, return_loss=False)
         if drop is not None:
@@ -608,10 +615,12 @@ class BERT(nn.Module):
     @torch.no_grad()
     def mask_predict(self, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1,
                      mp_config=None, long_mode='long', _race=None, _trace=None, given=None, _given_unknown=None, uncond_emb=None,
-                     guidance_scale=None, top_k=None, top_p=None, seeds=None, _substream=None, **kwargs):
+                     guidance_scale=None, top_k=None, top_p=None, seeds=None, _substream=None, video_top_k=None, video_top_p=None,
+                     video_temperature=None, **kwargs):
         """dalle_bert.py:514-714, batched over videos and beam candidates on the device (mmvid_amd/sampling.py).  `given` = (mask
         [b, TS], tokens [b, TS]): per-video known tokens (mmvid_amd/completion.py).  `uncond_emb` [b, csl, E] with `guidance_scale`:
-        classifier-free guidance; `top_k`, `top_p`: truncated sampling (both: sampling.mask_predict).
+        classifier-free guidance; `top_k`, `top_p`: truncated sampling; `video_top_k`, `video_top_p`: their per-video forms
+        (all: sampling.mask_predict).
 
         `seeds` (a sequence or integer tensor of b values in [0, 2^63), one per video): the token race, the Gumbel noise and the keep
         race of a video draw variates that are a function of its seed, the step and the (candidate, position, class) index
@@ -623,4 +632,5 @@ class BERT(nn.Module):
         return sampling.mask_predict(self, control_emb, dynamic=dynamic, debug=debug, steps=steps, preserve=preserve,
                                      t_overlap=t_overlap, mp_config=mp_config, long_mode=long_mode, race=_race, trace=_trace,
                                      given=given, given_unknown=_given_unknown, uncond_emb=uncond_emb, guidance_scale=guidance_scale,
-                                     top_k=top_k, top_p=top_p)
+                                     top_k=top_k, top_p=top_p, video_top_k=video_top_k, video_top_p=video_top_p,
+                                     video_temperature=video_temperature)

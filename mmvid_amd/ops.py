@@ -701,7 +701,7 @@ def _guided_operands(name, logits_c, logits_u, scale, rows_per_scale):
     assert all(t.dtype == f32 and t.is_cuda and t.stride(1) == 1 for t in (logits_c, logits_u))
     R, V = logits_c.shape
     if tuple(logits_u.shape) != (R, V) or logits_u.stride(0) != logits_c.stride(0):
-        if name == 'logits_truncate':  # (its `rows` check has taken the shape, and it calls the conditional operand `logits`)
+        if name in ('logits_truncate', 'logits_truncate_rows'):  # (its `rows` check has taken the shape, and it calls the conditional operand `logits`)
             raise ValueError(f'{name}: logits_u (row stride {logits_u.stride(0)}) must have the row stride of logits ({logits_c.stride(0)})')
         raise ValueError(f'{name}: logits_u {tuple(logits_u.shape)} (row stride {logits_u.stride(0)}) must have the shape and '
                          f'the row stride of logits_c {(R, V)} ({logits_c.stride(0)})')
@@ -774,6 +774,50 @@ def logits_truncate(logits, top_k=None, top_p=None, *, logits_u=None, scale=None
     call('mmvid_logits_truncate', _p(logits), _p(logits_u), logits.stride(0) if R > 1 else V, _p(scale),
          rows_per_scale if logits_u is not None else 1, float(logit_div), k, p, R, V, _p(out), out.stride(0) if R > 1 else V, _p(kept),
          _stream())
+    return (out, kept) if want_kept else out
+
+
+def logits_truncate_rows(logits, *, top_k=None, top_p=None, rows_k=None, rows_p=None, rows_inv_div=None, rows_per_param, divide_out=False,
+                         logits_u=None, scale=None, rows_per_scale=None, logit_div=1.0, out=None, want_kept=False):
+    """logits_truncate with the filter settings of a row read on the device (include/mmvid_hip_ext.h): rows_k int32, rows_p f32, rows_inv_div
+    f32, each [R // rows_per_param] on the device of `logits` or None, entry r // rows_per_param for row r.  None: the scalar (top_k,
+    top_p, 1 / logit_div) holds for every row.  Device values: a k outside [1, V) and a p >= 1 switch their filter off for the row;
+    rows_inv_div holds 1 / temperature as the host rounds it in fp32.  divide_out: a kept entry is g * inv_div (one rounded product),
+    so the race that follows runs with logit_div = 1.  With no array and divide_out False the result is logits_truncate's, byte for byte."""
+    def rows(t, name, shape=None):
+        _chk(t[:1], f32, name)
+        if t.dim() != 2 or t.stride(1) != 1 or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f'logits_truncate_rows: {name} must be f32 {shape or "[R, V]"} with unit column stride, got {tuple(t.shape)}')
+
+    rows(logits, 'logits')
+    R, V = logits.shape
+    k = 0 if top_k is None else min(int(top_k), V)
+    p = 1.0 if top_p is None else float(top_p)
+    rows_per_param = int(rows_per_param)
+    if rows_per_param <= 0 or R % rows_per_param:
+        raise ValueError(f'logits_truncate_rows: R = {R} rows is no multiple of rows_per_param = {rows_per_param}')
+    for t, name, dt in ((rows_k, 'rows_k', torch.int32), (rows_p, 'rows_p', f32), (rows_inv_div, 'rows_inv_div', f32)):
+        if t is None:
+            continue
+        _chk(t, dt, name)
+        if t.device != logits.device or tuple(t.shape) != (R // rows_per_param, ):
+            raise ValueError(f'logits_truncate_rows: {name} must be {dt} [R // rows_per_param] = [{R // rows_per_param}] on {logits.device}, '
+                             f'got {tuple(t.shape)} on {t.device}')
+    if (logits_u is None) != (scale is None) or (logits_u is None) != (rows_per_scale is None):
+        raise ValueError('logits_truncate_rows: logits_u, scale and rows_per_scale come together (the guided form)')
+    if logits_u is not None:
+        rows(logits_u, 'logits_u', (R, V))
+        rows_per_scale = _guided_operands('logits_truncate_rows', logits, logits_u, scale, rows_per_scale)[2]
+    if out is None:
+        out = torch.empty(R, V, device=logits.device, dtype=f32)
+    else:
+        rows(out, 'out', (R, V))
+    kept = torch.empty(R, device=logits.device, dtype=torch.int32) if want_kept else None
+    if R == 0:  # (an empty tensor has no address to pass)
+        return (out, kept) if want_kept else out
+    call('mmvid_logits_truncate_rows', _p(logits), _p(logits_u), logits.stride(0) if R > 1 else V, _p(scale),
+         rows_per_scale if logits_u is not None else 1, float(logit_div), k, p, _p(rows_k), _p(rows_p), _p(rows_inv_div), rows_per_param,
+         int(bool(divide_out)), R, V, _p(out), out.stride(0) if R > 1 else V, _p(kept), _stream())
     return (out, kept) if want_kept else out
 
 

@@ -190,6 +190,105 @@ def check_truncation_artv(top_k, top_p, V):
     return (k, p) if (k is not None and k < V) or (p is not None and p < 1.0) else None
 
 
+class VideoParams:
+    """What check_video_params returns: host arrays, [b] for ART-V and [Tmax, b] for BERT, each None when its keyword is.  k int32 (0: off;
+    a k >= V is stored as 0), p fp32 (1: off), inv_div fp32 [b] (1 / temperature as fp32 rounds it).  on(t): can a filter remove a class
+    of some video at step t -- known from the host values, so a step with nothing on takes the path without the keywords."""
+
+    def __init__(self, k, p, inv_div):
+        self.k, self.p, self.inv_div = k, p, inv_div
+
+    def on(self, t=None):
+        k, p = (self.k, self.p) if t is None else (None if self.k is None else self.k[t], None if self.p is None else self.p[t])
+        return bool((k is not None and (k >= 1).any()) or (p is not None and (p < 1).any()))
+
+    def device(self, dev):
+        """-> (k, p, inv_div) on `dev`, the arrays the kernel reads (built once per call)."""
+        return tuple(None if a is None else torch.from_numpy(a).to(dev) for a in (self.k, self.p, self.inv_div))
+
+
+def check_video_params(video_top_k, video_top_p, video_temperature, b, V, Tmax=None, top_k=None, top_p=None, temperature=1.0):
+    """The argument rules of the per-video sampling keywords, before any device work -> a VideoParams, or None when all three are None.
+    check_truncation keeps the scalar keywords (a tensor there is still refused); these are their per-video forms under names of their own.
+
+    Accepted for each: a sequence or a tensor of b entries, one per video; with Tmax (the mask-predict sampler) also [Tmax, b], one row per
+    step, step 0 included, as guidance_table takes it.  A None entry of a sequence, a k of 0 and a p of 1 switch the filter off for that
+    video (and step); a None temperature entry is 1.  A tensor on a device is read back once: the values are checked here, never on the
+    device.  ValueError: a wrong length or shape; a bool; a negative or non-integer k; a p outside (0, 1] or not finite (or one that
+    rounds to 0 in fp32); a temperature that is not finite and > 0 (or whose fp32 reciprocal is not); the scalar and the per-video form of
+    one quantity together (top_k with video_top_k, top_p with video_top_p, a temperature other than 1 with video_temperature);
+    video_temperature with Tmax (the mask-predict sampler has no softmax temperature to set per video)."""
+    if video_top_k is None and video_top_p is None and video_temperature is None:
+        return None
+    if video_temperature is not None and Tmax is not None:
+        raise ValueError('video_temperature: not accepted by the mask-predict sampler (its `temperature` schedule scales the noise on the '
+                         'confidences; there is no per-video softmax temperature)')
+    for scalar, video, name in ((top_k, video_top_k, 'top_k'), (top_p, video_top_p, 'top_p')):
+        if scalar is not None and video is not None:
+            raise ValueError(f'{name} and video_{name}: pass the scalar or the per-video form of one quantity, not both')
+    if video_temperature is not None and not (isinstance(temperature, (int, float, np.integer, np.floating)) and float(temperature) == 1.0):
+        raise ValueError('temperature and video_temperature: video_temperature replaces temperature, which must stay 1')
+
+    def one_k(v):
+        if v is None:
+            return 0
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f'video_top_k: expected integers >= 0 (0 or None: off), got {v!r}')
+        return int(v) if v < V else 0
+
+    def one_p(v):
+        if v is None:
+            return 1.0
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) <= 1.0 or \
+                not float(np.float32(v)) > 0.0:
+            raise ValueError(f'video_top_p: expected finite floats in (0, 1] (1 or None: off), got {v!r}')
+        return float(v)
+
+    def one_t(v):
+        if v is None:
+            return 1.0
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(float(v)) and float(v) > 0.0
+        if ok:
+            with np.errstate(all='ignore'):
+                inv = np.float32(1.0) / np.float32(v)
+            ok = bool(np.isfinite(inv)) and float(inv) > 0.0
+        if not ok:
+            raise ValueError(f'video_temperature: expected finite floats > 0 with a finite fp32 reciprocal, got {v!r}')
+        return float(v)
+
+    def as_lists(value, name, integers):
+        """A tensor, an array or a (nested) sequence as (nested) lists of Python scalars; the dtype of a tensor or an array is checked here."""
+        if torch.is_tensor(value) or isinstance(value, np.ndarray):
+            if torch.is_tensor(value):
+                kind = 'b' if value.dtype == torch.bool else ('f' if value.dtype.is_floating_point or value.dtype.is_complex else 'i')
+            else:
+                kind = value.dtype.kind
+            if kind == 'b' or (integers and kind not in 'iuO'):
+                raise ValueError(f'{name}: values of {value.dtype} are not accepted' + (' (expected integers)' if integers else ''))
+            return (value.detach().cpu() if torch.is_tensor(value) else value).tolist()
+        if isinstance(value, (list, tuple)):
+            return [as_lists(v, name, integers) if isinstance(v, (list, tuple, np.ndarray)) or torch.is_tensor(v) else v for v in value]
+        return value
+
+    def table(value, name, one, dtype, steps):
+        if value is None:
+            return None
+        want = f'{b} entries, one per video' + (f', or [Tmax, b] = [{steps}, {b}]' if steps is not None else '')
+        vals = as_lists(value, name, one is one_k)
+        if isinstance(vals, list) and len(vals) == b and not any(isinstance(v, list) for v in vals):
+            row = np.array([one(v) for v in vals], dtype)
+            return row if steps is None else np.ascontiguousarray(np.broadcast_to(row, (steps, b)))
+        if steps is not None and isinstance(vals, list) and len(vals) == steps and all(isinstance(r, list) and len(r) == b and
+                                                                                       not any(isinstance(v, list) for v in r) for r in vals):
+            return np.array([[one(v) for v in r] for r in vals], dtype)
+        raise ValueError(f'{name}: expected {want}, got {type(value).__name__}' + (f' {tuple(value.shape)}' if hasattr(value, 'shape') else ''))
+
+    k = table(video_top_k, 'video_top_k', one_k, np.int32, Tmax)
+    p = table(video_top_p, 'video_top_p', one_p, np.float32, Tmax)
+    temp = table(video_temperature, 'video_temperature', one_t, np.float32, None)
+    return VideoParams(k, p, None if temp is None else (np.float32(1.0) / temp).astype(np.float32))
+
+
 def check_guidance_artv(num_visuals, text_seq_len, total_tokens, num_image_tokens, B, guidance_scale, guidance_drop, negative_text, filter_thres):
     """The ART-V sampler's guidance keywords (check_guidance and the rules of the token loop, before any device work) -> (drop, scale),
     or None for the unguided call.  scale: a float, or a tensor [B] with one scale per video."""
@@ -239,7 +338,7 @@ def unconditional_inputs(text, visual, drop, negative_text):
 @torch.no_grad()
 def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preserve=None, t_overlap=1, mp_config=None,
                  long_mode='long', race=None, trace=None, given=None, given_unknown=None, uncond_emb=None, guidance_scale=None,
-                 top_k=None, top_p=None):
+                 top_k=None, top_p=None, video_top_k=None, video_top_p=None, video_temperature=None):
     """-> (tokens [b, TS] int64, image_samples list).  `race(name, shape)` supplies the Exp(1) variates (default: the
     device generator); `trace` (a list) receives one dict of the step's tensors per step (tests).
 
@@ -257,7 +356,13 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
 
     `top_k`, `top_p` (see check_truncation): at a step with a filter on, the logits (the guided value when guided) first go through
     ops.logits_truncate and the plain race then draws from what is left, so `Y` is the confidence under the truncated distribution.
-    A step with both off, and a call with both None, is the code path without them."""
+    A step with both off, and a call with both None, is the code path without them.
+
+    `video_top_k`, `video_top_p` (see check_video_params: b values, or [Tmax, b]): the per-video forms.  Two device tables [Tmax, b]
+    are built once before the loop; at a step where some video has a filter on, ONE ops.logits_truncate_rows stands where
+    ops.logits_truncate would, and every row reads the values of its video (rows_per_param = candidates * TS).  A scalar of the other
+    quantity composes.  A step at which no video has a filter on is the step without the per-video keywords (the host values say so).
+    `video_temperature` is refused here."""
     if (uncond_emb is None) != (guidance_scale is None):
         raise ValueError('mask_predict: uncond_emb and guidance_scale come together (both, or neither)')
     guided = uncond_emb is not None
@@ -273,6 +378,8 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
     trunc = check_truncation(top_k, top_p, Tmax, V)
     # the steps at which a filter can remove a class; at the others (k >= V, p = 1, None) the draw is the one without the keywords
     trunc_on = [False] * Tmax if trunc is None else [(k is not None and k < V) or (p is not None and p < 1.0) for k, p in zip(*trunc)]
+    video = check_video_params(video_top_k, video_top_p, video_temperature, b, V, Tmax, top_k, top_p)
+    rows_on = [False] * Tmax if video is None else [video.on(t) for t in range(Tmax)]
     if given is None:
         N, fixed, fixed_tok = preserved_tokens(model, b, preserve, t_overlap, long_mode, dev)
         n, temp = schedule(mp_config, N)
@@ -289,6 +396,8 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
         if tuple(uncond_emb.shape) != (b, csl, E):
             raise ValueError(f'uncond_emb: expected the shape of control_emb {(b, csl, E)}, got {tuple(uncond_emb.shape)}')
         scale = guidance_table(guidance_scale, Tmax, b, dev)
+    if any(rows_on):
+        rows_k, rows_p, _ = video.device(dev)  # int32 / fp32 [Tmax, b]: row t is what step t reads
 
     control_emb = ops._chk(control_emb.contiguous().float(), torch.float32, 'control_emb')
     if guided:
@@ -305,13 +414,19 @@ def mask_predict(model, control_emb, dynamic=True, debug=False, steps=10, preser
 
     truncated = {}  # what the truncated draw of the current step read: {'logits_t', 'kept'} (the trace keeps it)
 
+    def trunc_of(t, nb):  # the `trunc` of step t's draw: per-row where a video has a filter on, else the scalar pair, else None
+        if rows_on[t]:
+            k, p = (trunc[0][t], trunc[1][t]) if trunc is not None else (None, None)
+            return token_draw.RowParams(nb * TS, None if rows_k is None else rows_k[t], None if rows_p is None else rows_p[t], top_k=k, top_p=p)
+        return (trunc[0][t], trunc[1][t]) if trunc_on[t] else None
+
     def draw_tokens(logits, logits_u, t, nb):  # step t, nb candidates per video -> (tokens, Y, the race variates)
         truncated.clear()
         shape = (b * nb * TS, V)
         Et = draw(f'tok{t}', shape)
         noise_u = None if temp[t] == 0.0 else (race(f'tok{t}_noise_u', shape) if race is not None else torch.rand(shape, device=dev))
         return (*token_draw.draw(logits, Et, logits_u=logits_u, scale=scale[t] if guided else None, rows_per_scale=nb * TS, noise_u=noise_u,
-                                 temperature=temp[t], trunc=(trunc[0][t], trunc[1][t]) if trunc_on[t] else None, want_y=True,
+                                 temperature=temp[t], trunc=trunc_of(t, nb), want_y=True,
                                  record=truncated if trace is not None else None), Et)
 
     # ---- step 0: everything that is not given is [MASK]
