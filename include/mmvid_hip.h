@@ -23,6 +23,11 @@ extern "C" {
  * binding reads it from here and refuses a library built from another value. */
 #define MMVID_ABI_VERSION 3
 
+/* Trainer telemetry (mmvid_segment_stats, declared in mmvid_hip_ext.h, which holds functions only): the elements of one chunk of a
+ * segment, and the largest number of segments one call takes. */
+#define MMVID_TELEMETRY_CHUNK 4096
+#define MMVID_TELEMETRY_MAX_SEGMENTS 65536
+
 const char* mmvid_last_error(void);
 int mmvid_abi_version(void);
 int mmvid_device_count(void);

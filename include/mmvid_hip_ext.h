@@ -126,6 +126,74 @@ int mmvid_logits_truncate_rows(const float* logits, const float* logits_u, int64
                                const float* inv_div_dev, int64_t rows_per_param, int divide_out, int64_t R, int V,
                                float* out, int64_t ld_out, int32_t* kept, void* stream);
 
+/* ---- Trainer telemetry: per-parameter gradient, weight and update statistics, taken on the device after the optimiser ----------------
+ *
+ * The rule (csrc/telemetry.hip; tests/telemetry_ref.py is the host replica, bit for bit).  g, p, m, v are the flat fp32 buffers of
+ * mmvid_adam_step_rows, n elements each, as the optimiser LEFT them; they are only read.  CHUNK = MMVID_TELEMETRY_CHUNK (mmvid_hip.h).
+ *
+ * Segments and chunks.  Segment s (0 <= s < segments: one parameter) is the range [seg_off[s], seg_off[s] + seg_len[s]) of the flat
+ * buffers: offsets are multiples of 128 elements, lengths are >= 1, what lies between two segments belongs to none and is never read.
+ * A segment of length L is cut into ceil(L / CHUNK) chunks; chunk k of it covers its elements [k CHUNK, min(L, (k + 1) CHUNK)) and has
+ * the global index seg_chunk0[s] + k.  seg_chunk0 is ascending (seg_chunk0[0] = 0, seg_chunk0[s + 1] = seg_chunk0[s] + the chunks of s)
+ * and `chunks` is the total.  The three tables are int64 [segments] on the device.
+ *
+ * Statistics of a segment.  Over the elements the optimiser touched -- all of them, but for the rows of the lazy table (below) whose
+ * flag is 0 -- with "finite" meaning neither NaN nor +-inf:
+ *     g_sumsq     sum of g * g over the finite g               g_absmax   max of |g| over the finite g (+0 where there is none)
+ *     g_nonfinite the number of g that are NaN or +-inf        g_count    the number of g looked at, finite or not       (both int32)
+ *     d_sumsq     sum of d * d, d the update this step applied to the element, recomputed from the state Adam left:
+ *                     lr = lr_dev ? *lr_dev : lr ;  t = step_dev ? *step_dev : (float)step
+ *                     bc1 = 1.f - powf(beta1, t) ;  bc2s = sqrtf(1.f - powf(beta2, t))     (with step_dev: the device's powf, as in the
+ *                                                                                            Adam kernel; else computed by the host)
+ *                     d = ((lr / bc1) * m) / (sqrtf(v) / bc2s + eps)                         every operation one rounded fp32 operation,
+ *                                                                                            none contracted; lr / bc1 is formed once
+ *                 (L2 weight decay sits inside m, so the formula holds with it.)  With skip_dev != NULL and *skip_dev != 0 (the verdict
+ *                 of mmvid_step_guard: no update happened) d_sumsq is +0 for every segment and m, v are not read; the g statistics are
+ *                 taken as ever -- they say where the non-finite values sit.
+ * and over ALL elements of the segment:
+ *     p_sumsq     sum of p * p
+ * Lazy rows: row_flags, table_lo, table_rows, rowlen as in mmvid_adam_step_rows.  A row whose flag is 0 adds nothing to the g
+ * statistics, g_count and d_sumsq (Adam did not touch it; g, m, v are not read there) and adds to p_sumsq like any other.
+ *
+ * Summation order: a function of a segment's length and CHUNK only -- never of the grid, the CU count or an arrival order; no
+ * floating-point atomics.  Every product and sum below is one rounded fp32 operation.  A term that does not count (a non-finite g, an
+ * unflagged row, a skipped step, an element past the end of the segment) is +0.
+ *   Pass 1, a chunk (256 threads; thread T, trip r = 0..3, lane e = 0..3 hold element j = 1024 r + 4 T + e of the chunk):
+ *     q(T, r) = (x0 x0 + x1 x1) + (x2 x2 + x3 x3)                            the four elements of a thread's trip
+ *     a(T)    = (((0 + q(T, 0)) + q(T, 1)) + q(T, 2)) + q(T, 3)              a thread, its trips in order
+ *     w(W)    = the halving tree over the 64 threads of wave W = T / 64:     x[i] + x[i + 32] for i < 32, then + 16, 8, 4, 2, 1
+ *     chunk   = (w(0) + w(1)) + (w(2) + w(3))
+ *   Pass 2, a segment of C chunks with the chunk sums c[0..C):
+ *     a(T)    = ((0 + c[T]) + c[T + 256]) + c[T + 512] ...                   thread T, every 256th chunk in order (+0 where T >= C)
+ *     then the wave trees and the sum of the four waves, as in pass 1.
+ * Maxima and counts are order-free and exact.  The record's total is the sum of g_sumsq over the segments by the pass-2 rule with the
+ * segments in the place of the chunks.
+ *
+ * The ring.  count = count_dev[0] counts calls (an int32 on the device, zeroed by the caller before the first call; taken as unsigned).
+ * When count % every != 0 the call writes nothing but count_dev[0] = count + 1: every thread of passes 1 and 2 returns before its
+ * first load on that scalar.  Otherwise the record goes to slot k = (count / every) % slots of
+ *     ring_f [slots][segments][4]   g_sumsq, g_absmax, p_sumsq, d_sumsq              ring_i [slots][segments][2]   g_nonfinite, g_count
+ *     head_i [slots][4]             count, (int)t, the skip verdict (0 / 1), 1       head_f [slots][2]             lr, the record's total
+ * and count_dev[0] = count + 1 follows, in a last launch of one block on the stream: at most three launches and no host input, so a
+ * captured step fills the ring by itself.  partials_f (fp32 [chunks][4]) and partials_i (int32 [chunks][2]) are the per-chunk results
+ * between the passes, overwritten by every call that is not gated.  The caller zeroes head_i once: a slot is valid where head_i[k][3] is 1.
+ *
+ * Table values are data.  seg_off is read rounded down to a multiple of 4 and clipped to [0, n], seg_len clipped to [0, n - offset], a
+ * chunk index formed from seg_chunk0 clipped to [0, chunks): a corrupt table gives wrong numbers for the segments it concerns and no
+ * access outside the buffers.  Every store index comes from the launch geometry, segments, chunks, slots and count_dev.
+ *
+ * Refused with an error (never a fault, nothing launched, nothing written): a NULL g, p, m, v, table, count_dev, partials, ring or
+ * head pointer; g, p, m or v not 16-byte aligned, a table not 8-byte aligned, any other pointer not 4-byte aligned; n < 0; segments
+ * outside [1, MMVID_TELEMETRY_MAX_SEGMENTS]; chunks < segments or chunks > n / CHUNK + segments (no plan has more); every < 1;
+ * slots < 1; step < 1 without step_dev; beta1 or beta2 outside [0, 1) or NaN; a lazy table that does not lie inside [0, n) or whose
+ * table_lo or rowlen is not a multiple of 4.  n == 0: nothing is launched, count_dev included. */
+int mmvid_segment_stats(const float* g, const float* p, const float* m, const float* v, int64_t n,
+                        const int64_t* seg_off, const int64_t* seg_len, const int64_t* seg_chunk0, int32_t segments, int64_t chunks,
+                        float lr, const float* lr_dev, float beta1, float beta2, float eps, int step, const float* step_dev,
+                        const uint8_t* row_flags, int64_t table_lo, int64_t table_rows, int rowlen, const int32_t* skip_dev,
+                        int32_t every, int32_t slots, int32_t* count_dev, float* partials_f, int32_t* partials_i,
+                        float* ring_f, int32_t* ring_i, int32_t* head_i, float* head_f, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

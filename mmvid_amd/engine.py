@@ -60,11 +60,26 @@ def refuse_unproven_width(model, what):
                                   'memory-access fault at width 1024 and its cause is not known)')
 
 
+def telemetry_group(name):
+    """The group a parameter's telemetry falls into under `telemetry(by='layer')`: 'layer.<i>' for everything of tower layer i
+    (`transformer.transformer.resblocks.<i>.*`), 'heads' for the output heads (`to_logits*`), 'tables' for the rest -- the embedding
+    and positional tables.  The same three kinds as `backward_order`."""
+    if name.startswith('transformer.transformer.resblocks.'):
+        return f'layer.{int(name.split(".")[3])}'
+    return 'heads' if name.startswith('to_logits') else 'tables'
+
+
 class FlatTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  process_group=None, bucket_mb=64, order=None, lr_schedule=None, force_exchange=False, sparse_tables=True,
-                 lazy_rows=True, exchange=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False):
+                 lazy_rows=True, exchange=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False,
+                 telemetry_every=None, telemetry_slots=64):
         self.model = model
+        # trainer telemetry (INTEGRATION.md "Trainer telemetry"): None = off -- no buffer, no launch, state_dict() unchanged key for key
+        for key, val in (('telemetry_every', telemetry_every), ('telemetry_slots', telemetry_slots)):
+            if (val is not None or key == 'telemetry_slots') and (isinstance(val, bool) or not isinstance(val, int) or val < 1):
+                raise ValueError(f'{key}={val!r}: an int >= 1' + (', or None for no telemetry' if key == 'telemetry_every' else ''))
+        self.telemetry_every, self.telemetry_slots = telemetry_every, telemetry_slots
         # non-finite guard (INTEGRATION.md "Non-finite guard"): False = off -- no buffer, the unguarded step's launches, state_dict() unchanged
         if not isinstance(skip_nonfinite, bool):
             raise ValueError(f'skip_nonfinite={skip_nonfinite!r}: True or False')
@@ -134,6 +149,11 @@ class FlatTrainer:
         guarded = self.skip_nonfinite and dev.type == 'cuda'
         self.guard_i = torch.zeros(4, device=dev, dtype=torch.int32) if guarded else None
         self.guard_f = torch.zeros(2, device=dev, dtype=torch.float32) if guarded else None
+        self._tel = None
+        if telemetry_every is not None:
+            if dev.type != 'cuda':
+                raise ValueError('telemetry_every on a host trainer: it has no optimiser kernel to take the statistics after')
+            self._init_telemetry(dev)
         self._comm_stream = torch.cuda.Stream(device=dev) if dev.type == 'cuda' else None
         self._works = []
         self._sent_from = tot  # gradients at flat offsets >= this are already on the wire this step
@@ -149,6 +169,73 @@ class FlatTrainer:
         if tw is not None and hasattr(tw, 'on_layers_done') and self._layer_start and (self.world > 1 or self.force_exchange):
             tw.on_layers_done = self.layers_done
         self._init_lazy_rows(lazy_rows and os.environ.get('MMVID_LAZY_ROWS', '1') != '0')
+
+    # ------------------------------------------------------------------------------------------------ telemetry
+    def _init_telemetry(self, dev):
+        """The segment tables (one segment per parameter, uploaded once), the counter, the per-chunk partials and the ring of
+        mmvid_segment_stats.  The ring is diagnostics, not state: it is in no checkpoint and a resumed trainer starts with an empty one."""
+        off, ln, c0, chunks = ops.telemetry_plan(self.offsets, [p.numel() for p in self.params])
+        S, slots = len(off), self.telemetry_slots
+        i32 = dict(device=dev, dtype=torch.int32)
+        self._tel = {'tables': tuple(torch.tensor(t, dtype=torch.int64).to(dev) for t in (off, ln, c0)), 'chunks': chunks,
+                     'count': torch.zeros(1, **i32), 'partials_f': torch.zeros(chunks * 4, device=dev), 'partials_i': torch.zeros(chunks * 2, **i32),
+                     'ring_f': torch.zeros(slots * S * 4, device=dev), 'ring_i': torch.zeros(slots * S * 2, **i32),
+                     'head_i': torch.zeros(slots * 4, **i32), 'head_f': torch.zeros(slots * 2, device=dev)}
+
+    def _telemetry_read(self):
+        """Every valid record of the ring, oldest first, as (head_i [4], head_f [2], ring_f [S, 4], ring_i [S, 2]) of host tensors -- one
+        device read.  It touches the ring only, nothing `ema_weights()` re-points: allowed inside that scope."""
+        t = self._tel
+        if t is None:
+            raise RuntimeError('this trainer takes no telemetry (telemetry_every=None)')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('telemetry is read inside a stream capture: it reads the device')
+        S, slots = len(self.names), self.telemetry_slots
+        raw = torch.cat([t['head_i'], t['head_f'].view(torch.int32), t['ring_f'].view(torch.int32), t['ring_i']]).cpu()
+        hi, hf = raw[:slots * 4].view(slots, 4), raw[slots * 4:slots * 6].view(torch.float32).view(slots, 2)
+        rf = raw[slots * 6:slots * 6 + slots * S * 4].view(torch.float32).view(slots, S, 4)
+        ri = raw[slots * 6 + slots * S * 4:].view(slots, S, 2)
+        valid = sorted((int(hi[k, 0]), k) for k in range(slots) if int(hi[k, 3]) == 1)
+        return [(hi[k], hf[k], rf[k], ri[k]) for _, k in valid]
+
+    def telemetry(self, last=None, by='param'):
+        """The telemetry records the ring holds, oldest first (at most the `last` newest), in one device read (it synchronises).  A
+        record: 'record' (the number of the step() call, from 0), 'step' (applied optimiser steps, that one included), 'skipped' (the
+        non-finite guard's verdict), 'lr', 'grad_norm' (sqrt of the sum over the FINITE gradient elements, / world: what
+        guard_stats()['grad_norm'] reports for a step it did not skip) and 'params': name -> 'grad_norm', 'grad_absmax' (both / world),
+        'grad_nonfinite', 'weight_norm', 'update_norm' (0 on a skipped step) and 'update_ratio' = update_norm / weight_norm.  by='layer'
+        merges the parameters by `telemetry_group` (squares summed, maxima taken, counts added).  Roots, the 1 / world scaling and the
+        ratio are taken in fp64 on the host."""
+        if by not in ('param', 'layer'):
+            raise ValueError(f"by={by!r}: 'param' or 'layer'")
+        if last is not None and (isinstance(last, bool) or not isinstance(last, int) or last < 1):
+            raise ValueError(f'last={last!r}: an int >= 1, or None for every record')
+        recs = self._telemetry_read()
+        out = []
+        for hi, hf, rf, ri in (recs if last is None else recs[-last:]):
+            rf, ri = rf.double(), ri.tolist()
+            merged = {}
+            for s, name in enumerate(self.names):
+                key = name if by == 'param' else telemetry_group(name)
+                a = merged.setdefault(key, [0.0, 0.0, 0.0, 0.0, 0])
+                a[0] += float(rf[s, 0]); a[1] = max(a[1], float(rf[s, 1])); a[2] += float(rf[s, 2]); a[3] += float(rf[s, 3]); a[4] += ri[s][0]
+            params = {}
+            for key, (gsq, gmax, psq, dsq, bad) in merged.items():
+                wn, un = psq**0.5, dsq**0.5
+                params[key] = {'grad_norm': gsq**0.5 / self.world, 'grad_absmax': gmax / self.world, 'grad_nonfinite': bad,
+                               'weight_norm': wn, 'update_norm': un, 'update_ratio': un / wn if wn > 0 else float('nan')}
+            out.append({'record': int(hi[0]), 'step': int(hi[1]), 'skipped': bool(int(hi[2])), 'lr': float(hf[0]),
+                        'grad_norm': float(hf[1].double())**0.5 / self.world, 'params': params})
+        return out
+
+    def first_nonfinite(self):
+        """The names of the parameters, in flat order, whose gradient held a NaN or an inf at the newest record; [] if none did (or no
+        record was taken yet)."""
+        recs = self._telemetry_read()
+        if not recs:
+            return []
+        bad = recs[-1][3][:, 0].tolist()
+        return [n for n, b in zip(self.names, bad) if b > 0]
 
     # ------------------------------------------------------------------------------------------ lazy table rows
     def _init_lazy_rows(self, enabled):
@@ -312,6 +399,9 @@ class FlatTrainer:
             saved = sd.get('guard') or {}
             self.guard_i.copy_(torch.tensor([0, int(saved.get('skipped', 0)), 0, int(saved.get('seen', 0))], dtype=torch.int32))
             self.guard_f.zero_()
+        if self._tel is not None:  # the ring is diagnostics, not state: a resumed trainer starts with an empty one
+            self._tel['head_i'].zero_()
+            self._tel['count'].zero_()
         g = sd['param_groups'][0]
         self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
         fe = getattr(self.model, 'frontend', None)
@@ -632,6 +722,12 @@ class FlatTrainer:
             skip = self.guard_i  # (element 0)
         ops.adam_step(self.P, self.G, self.M, self.V, self.S, self.step_count, self.lr, self.betas, self.eps, self.wd,
                       self.max_norm, self._sq, gscale, step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg(), skip_dev=skip)
+        if self._tel is not None:  # same stream, after Adam, with the scalars, the lazy rows and the verdict Adam got; it only reads
+            t = self._tel
+            ops.segment_stats(self.G, self.P, self.M, self.V, t['tables'], t['chunks'], self.step_count, self.lr, self.betas, self.eps,
+                              self.telemetry_every, self.telemetry_slots, t['count'], t['partials_f'], t['partials_i'], t['ring_f'],
+                              t['ring_i'], t['head_i'], t['head_f'], step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg(),
+                              skip_dev=skip)
         if self.E is not None:  # same stream, after Adam; t is read from the device counter: a captured step carries it as it stands
             ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, step_dev=self._step_dev, lazy=self._lazy_arg(),
                            skip_dev=skip)

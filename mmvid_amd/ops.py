@@ -504,6 +504,52 @@ def ema_update(ema, p, decay, warmup, step, step_dev=None, lazy=None, skip_dev=N
         call('mmvid_ema_update_guarded', *args, _p(_chk(skip_dev, torch.int32, 'skip_dev')), _stream())
 
 
+TELEMETRY_CHUNK = _lib.HEADER.constants['MMVID_TELEMETRY_CHUNK']  # elements of one chunk of a segment (include/mmvid_hip.h)
+
+
+def telemetry_plan(offsets, numels, chunk=TELEMETRY_CHUNK):
+    """The tables of mmvid_segment_stats for the segments [offsets[s], offsets[s] + numels[s]) of a flat buffer: (seg_off, seg_len,
+    seg_chunk0, chunks) -- three lists of ints, one entry per segment, and the total number of chunks.  Segment s is cut into
+    ceil(numels[s] / chunk) chunks, numbered from seg_chunk0[s] on; what lies between two segments is in no chunk.  Pure host code."""
+    offsets, numels, chunk = [int(o) for o in offsets], [int(n) for n in numels], int(chunk)
+    if len(offsets) != len(numels) or not offsets:
+        raise ValueError(f'telemetry_plan: {len(offsets)} offsets for {len(numels)} lengths (at least one segment)')
+    if chunk < 1 or any(n < 1 for n in numels) or any(o < 0 for o in offsets):
+        raise ValueError('telemetry_plan: the chunk and every length must be >= 1, every offset >= 0')
+    if any(offsets[s] + numels[s] > offsets[s + 1] for s in range(len(offsets) - 1)):
+        raise ValueError('telemetry_plan: the segments must be ascending and must not overlap')
+    chunk0, total = [], 0
+    for n in numels:
+        chunk0.append(total)
+        total += (n + chunk - 1) // chunk
+    return offsets, numels, chunk0, total
+
+
+def segment_stats(g, p, m, v, tables, chunks, step, lr, betas, eps, every, slots, count, partials_f, partials_i, ring_f, ring_i, head_i,
+                  head_f, step_dev=None, lr_dev=None, lazy=None, skip_dev=None):
+    """One telemetry record (include/mmvid_hip_ext.h: mmvid_segment_stats): per segment of the flat buffers sum g^2, max |g| and the
+    count of non-finite g, sum p^2 and the sum of squares of the update Adam just applied, into slot (count / every) % slots of the
+    ring -- or, where count % every != 0, nothing; count (int32 on the device) advances either way.  tables = (seg_off, seg_len,
+    seg_chunk0), int64 on the device, as telemetry_plan lays them out; step_dev, lr_dev, lazy and skip_dev are what adam_step got."""
+    for t, n in ((g, 'g'), (p, 'p'), (m, 'm'), (v, 'v'), (partials_f, 'partials_f'), (ring_f, 'ring_f'), (head_f, 'head_f')):
+        _chk(t, f32, n)
+    for t, n in ((count, 'count'), (partials_i, 'partials_i'), (ring_i, 'ring_i'), (head_i, 'head_i')):
+        _chk(t, torch.int32, n)
+    off, ln, c0 = (_chk(t, i64, 'segment table') for t in tables)
+    S = off.numel()
+    if not (g.numel() == m.numel() == v.numel() == p.numel()) or ln.numel() != S or c0.numel() != S:
+        raise ValueError('segment_stats: g, p, m, v must have one size and the three tables one length')
+    if (partials_f.numel() < 4 * chunks or partials_i.numel() < 2 * chunks or ring_f.numel() != slots * S * 4 or ring_i.numel() != slots * S * 2
+            or head_i.numel() != slots * 4 or head_f.numel() != slots * 2 or count.numel() < 1):
+        raise ValueError(f'segment_stats: buffers do not fit {S} segments, {chunks} chunks and {slots} slots')
+    fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
+    if skip_dev is not None:
+        _chk(skip_dev, torch.int32, 'skip_dev')
+    call('mmvid_segment_stats', _p(g), _p(p), _p(m), _p(v), p.numel(), _p(off), _p(ln), _p(c0), S, int(chunks), float(lr), _p(lr_dev),
+         float(betas[0]), float(betas[1]), float(eps), int(step), _p(step_dev), _p(fl), int(lo), int(rows), int(rowlen), _p(skip_dev),
+         int(every), int(slots), _p(count), _p(partials_f), _p(partials_i), _p(ring_f), _p(ring_i), _p(head_i), _p(head_f), _stream())
+
+
 def step_guard(sqnorm, grad_scale, step_dev, guard_i, guard_f):
     """The non-finite guard's verdict on the device (include/mmvid_hip_ext.h: mmvid_step_guard): guard_i (int32 [4]) = skip, skipped,
     run, seen; guard_f (fp32 [2]) = gradient norm, last finite gradient norm; step_dev advances only where the step is applied."""
