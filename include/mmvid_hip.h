@@ -216,7 +216,10 @@ int mmvid_adam_step_lr(float* p, const float* g, float* m, float* v, void* shado
  * of an embedding table, row_flags[r] != 0 marks the rows that have EVER received a gradient.  Unflagged rows have g = m = v = 0:
  * Adam without weight decay leaves them unchanged and they add nothing to the norm, so both kernels skip them -- exact, and 30 B
  * per skipped parameter less traffic (BERT's text embedding is 30 % of its parameters; a step touches <= 3*B*64 of 49,472 rows).
- * row_flags NULL = the plain kernels. */
+ * row_flags NULL = the plain kernels.  Refused, before anything is launched and at n == 0 too (by every entry that takes these four
+ * arguments): a table that does not lie inside [0, n) -- table_lo < 0, table_rows < 0, rowlen <= 0, table_lo > n or
+ * table_rows > (n - table_lo) / rowlen, a test no product can wrap -- or whose table_lo or rowlen is not a multiple of 4; by
+ * mmvid_adam_step_rows also a table together with weight_decay != 0. */
 int mmvid_grad_sqnorm_rows(const float* g, int64_t n, float* partials, float* out_accum, const uint8_t* row_flags,
                            int64_t table_lo, int64_t table_rows, int rowlen, void* stream);
 int mmvid_adam_step_rows(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,

@@ -4,29 +4,17 @@
 //   d = warmup ? fminf(decay, (1 + t) / (10 + t)) : decay ;  a = 1 - d          one fp32 operation each
 //   ema' = fmaf(a, p - ema, ema)                                                  exact where ema == p: the result is p
 // HBM-bound like the Adam kernel it follows (csrc/optim.hip): 12 B per parameter (p and ema read, ema written), one launch for the
-// whole model, 256 threads, float4, a grid-stride loop, a scalar tail for n % 4.  No atomics, no LDS.  A row of the lazy table (same
-// arguments and conditions as mmvid_adam_step_rows) whose flag is 0 is neither read nor written: the trainer keeps ema == p there,
-// where the update is the identity.
+// whole model, 256 threads, float4, a grid-stride loop, a scalar tail for n % 4.  No atomics, no LDS.  A row of the lazy table
+// (step_state.h: the table Adam got) whose flag is 0 is neither read nor written: the trainer keeps ema == p there, where the update
+// is the identity.
 // Two departures from the Adam kernel's loop, both measured at BERT's 124.7 M elements ("Weight EMA"): the grid is
 // capped at 512 blocks, not 2,048 (0.300 ms at 2,048, 0.282 at 1,024, 0.268 at 512 with plain loads), and every byte is touched once
 // per step, so loads and stores are nontemporal (0.229 ms at 512 blocks: 6.5 TB/s).  Unrolling the loop over two or four trips was
 // slower (0.325 / 0.416 ms).
 #include "../../include/mmvid_hip_ext.h"
-#include "common.h"
+#include "step_state.h"
 
 namespace {
-
-struct LazyRows {
-    const unsigned char* flags;  // null: no lazy table
-    long lo, hi;                 // element range of the table in the flat buffer
-    int rowlen;
-};
-__device__ __forceinline__ bool lazy_skip(const LazyRows& z, long i) {
-    return z.flags && i >= z.lo && i < z.hi && z.flags[(i - z.lo) / z.rowlen] == 0;
-}
-
-typedef __attribute__((ext_vector_type(4))) float f4_t;
-__device__ __forceinline__ f4_t load_once(const float* q) { return __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(q)); }
 
 __device__ __forceinline__ float ema_one(float a, float p, float e) {
     const float diff = __fsub_rn(p, e);  // (an explicit fp32 subtraction: never contracted into the fmaf)
@@ -36,18 +24,18 @@ __device__ __forceinline__ float ema_one(float a, float p, float e) {
 __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float decay, int warmup,
                                                   float t, const float* __restrict__ step_dev, LazyRows z,
                                                   const int* __restrict__ skip) {
-    if (skip && *skip) return;  // non-finite guard (mmvid_step_guard): a kernel argument's load, the same in every lane -- a scalar branch
-    if (step_dev) t = *step_dev;  // step count kept on the device: a captured step follows the warm-up without host input
+    if (step_skipped(skip)) return;
+    t = device_wins(step_dev, t);  // (a captured step follows the warm-up without host input)
     float d = decay;
     if (warmup) d = fminf(decay, __fdiv_rn(__fadd_rn(1.f, t), __fadd_rn(10.f, t)));
     const float a = __fsub_rn(1.f, d);
     const long stride = (long)gridDim.x * 256 * 4;
     for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
-        if (lazy_skip(z, i)) continue;  // (rowlen % 4 == 0 and lo % 4 == 0: the four elements share a row)
+        if (lazy_skip(z, i)) continue;
         if (i + 3 < n) {
-            const f4_t pp = load_once(p + i), ee = load_once(ema + i);
-            const f4_t out = {ema_one(a, pp.x, ee.x), ema_one(a, pp.y, ee.y), ema_one(a, pp.z, ee.z), ema_one(a, pp.w, ee.w)};
-            __builtin_nontemporal_store(out, reinterpret_cast<f4_t*>(ema + i));
+            const f32x4 pp = load_once(p + i), ee = load_once(ema + i);
+            const f32x4 out = {ema_one(a, pp.x, ee.x), ema_one(a, pp.y, ee.y), ema_one(a, pp.z, ee.z), ema_one(a, pp.w, ee.w)};
+            __builtin_nontemporal_store(out, reinterpret_cast<f32x4*>(ema + i));
         } else {
             for (long k = i; k < n; ++k) ema[k] = ema_one(a, p[k], ema[k]);
         }
@@ -70,14 +58,7 @@ static int ema_launch(float* ema, const float* p, int64_t n, float decay, int wa
     MMVID_REQUIRE(decay >= 0.f && decay < 1.f, "ema_update: decay=%g is outside [0, 1)", (double)decay);  // (false for NaN)
     MMVID_REQUIRE(step >= 1 || step_dev, "ema_update: step=%d must be >= 1 where no device step count is given", step);
     LazyRows z;
-    z.flags = nullptr, z.lo = z.hi = 0, z.rowlen = 1;
-    if (row_flags) {  // the conditions of csrc/optim.hip's make_lazy
-        MMVID_REQUIRE(table_lo >= 0 && table_rows >= 0 && rowlen > 0 && rowlen % 4 == 0 && table_lo % 4 == 0 && table_lo <= n &&
-                          table_rows <= (n - table_lo) / rowlen,
-                      "ema_update: lazy rows: the table [%lld, +%lld x %d) must lie inside the buffer and be 4-element aligned",
-                      (long long)table_lo, (long long)table_rows, rowlen);
-        z.flags = row_flags, z.lo = table_lo, z.hi = table_lo + table_rows * rowlen, z.rowlen = rowlen;
-    }
+    if (int rc = make_lazy(z, "ema_update", row_flags, table_lo, table_rows, rowlen, n)) return rc;
     if (n == 0) return MMVID_OK;
     long b = (long)((n + 1023) / 1024);
     if (b > 512) b = 512;  // (two blocks per CU: see the head of this file)

@@ -13,7 +13,7 @@
 //   finish  one block: the record's total (the pass-2 rule over the segments' g sums), the slot's header, count_dev += 1
 // The order is a function of the segment's length and the chunk size alone.  A gated call (count % every != 0) returns from passes 1
 // and 2 on a scalar branch before any load and only advances the counter.
-// HBM-bound: 16 B read per parameter, each byte once (nontemporal loads, as csrc/ema.hip), against the 28 B the Adam kernel moves.
+// HBM-bound: 16 B read per parameter, each byte once (load_once: nontemporal), against the 28 B the Adam kernel moves.
 // Pass 1 is bound by the bytes it keeps in flight, measured at BERT's 124.7 M elements ("Trainer telemetry"): a thread's
 // four trips unrolled (16 float4 loads issued before the first use) at 8 waves per SIMD -- __launch_bounds__(256, 8): 64 VGPRs, 76 B of
 // scratch per lane -- and 2,048 blocks take 0.356 ms (5.6 TB/s); the same loop at the 91 VGPRs it wants (5 waves) 0.414 ms with 1,024 or
@@ -22,7 +22,7 @@
 // Table values are data: every address formed from a table is clipped to the buffers, every store index comes from the launch.
 #include "../../include/mmvid_hip.h"
 #include "../../include/mmvid_hip_ext.h"
-#include "common.h"
+#include "step_state.h"
 
 // every product and sum of this file is the rounded fp32 operation it is written as: nothing is contracted into an fma
 #pragma clang fp contract(off)
@@ -31,15 +31,6 @@ namespace {
 
 constexpr long CHUNK = MMVID_TELEMETRY_CHUNK;
 static_assert(CHUNK == 4 * 256 * 4, "a chunk is four trips of 256 threads x 4 elements");
-
-struct LazyRows {
-    const unsigned char* flags;  // null: no lazy table
-    long lo, hi;                 // element range of the table in the flat buffer
-    int rowlen;
-};
-__device__ __forceinline__ bool lazy_skip(const LazyRows& z, long i) {
-    return z.flags && i >= z.lo && i < z.hi && z.flags[(i - z.lo) / z.rowlen] == 0;
-}
 
 struct Tables {
     const long* off;
@@ -64,9 +55,6 @@ struct Scalars {
     const int* skip;
 };
 
-typedef __attribute__((ext_vector_type(4))) float f4_t;
-__device__ __forceinline__ f4_t load_once(const float* q) { return __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(q)); }
-__device__ __forceinline__ bool finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ float quad(float a, float b, float c, float d) { return (a * a + b * b) + (c * c + d * d); }
 __device__ __forceinline__ float update_of(float stepsz, float m, float v, float bc2s, float eps) {
     return (stepsz * m) / (sqrtf(v) / bc2s + eps);
@@ -116,12 +104,11 @@ __global__ __launch_bounds__(256, 8) void segment_chunks_kernel(const float* __r
                                                              Scalars sc, LazyRows z, const int* __restrict__ count_dev, int every,
                                                              float* __restrict__ part_f, int* __restrict__ part_i) {
     if (gated(*count_dev, every)) return;  // a kernel argument's load, the same in every lane -- a scalar branch, before any other load
-    const bool skipped = sc.skip && *sc.skip;
-    if (sc.lr_dev) sc.lr = *sc.lr_dev;
-    if (sc.step_dev) {  // the bias corrections as adam_kernel (csrc/optim.hip) forms them from the device's step count
-        const float t = *sc.step_dev;
-        sc.bc1 = 1.0f - powf(sc.beta1, t);
-        sc.bc2s = sqrtf(1.0f - powf(sc.beta2, t));
+    const bool skipped = step_skipped(sc.skip);
+    sc.lr = device_wins(sc.lr_dev, sc.lr);
+    if (sc.step_dev) {
+        const BiasCorrections bc = bias_corrections(sc.beta1, sc.beta2, *sc.step_dev);
+        sc.bc1 = bc.bc1, sc.bc2s = bc.bc2_sqrt;
     }
     const float stepsz = sc.lr / sc.bc1;
     for (long c = blockIdx.x; c < tb.chunks; c += gridDim.x) {
@@ -150,21 +137,21 @@ __global__ __launch_bounds__(256, 8) void segment_chunks_kernel(const float* __r
             float pe[4] = {0.f, 0.f, 0.f, 0.f}, ge[4] = {0.f, 0.f, 0.f, 0.f}, de[4] = {0.f, 0.f, 0.f, 0.f};
             if (j + 3 < cnt) {  // (base is a multiple of 4 and so is the lazy table's geometry: the four elements share a row)
                 const bool lazy = lazy_skip(z, i);
-                const f4_t pp = load_once(p + i);
+                const f32x4 pp = load_once(p + i);
                 pe[0] = pp.x, pe[1] = pp.y, pe[2] = pp.z, pe[3] = pp.w;
                 if (!lazy) {
-                    const f4_t gg = load_once(g + i);
+                    const f32x4 gg = load_once(g + i);
                     float gr[4] = {gg.x, gg.y, gg.z, gg.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const bool f = finite(gr[e]);
+                        const bool f = finite_bits(gr[e]);
                         ge[e] = f ? gr[e] : 0.f;
                         a.nonfinite += f ? 0 : 1;
                         a.gmax = fmaxf(a.gmax, fabsf(ge[e]));
                     }
                     a.count += 4;
                     if (!skipped) {
-                        const f4_t mm = load_once(m + i), vv = load_once(v + i);
+                        const f32x4 mm = load_once(m + i), vv = load_once(v + i);
                         de[0] = update_of(stepsz, mm.x, vv.x, sc.bc2s, sc.eps), de[1] = update_of(stepsz, mm.y, vv.y, sc.bc2s, sc.eps);
                         de[2] = update_of(stepsz, mm.z, vv.z, sc.bc2s, sc.eps), de[3] = update_of(stepsz, mm.w, vv.w, sc.bc2s, sc.eps);
                     }
@@ -174,7 +161,7 @@ __global__ __launch_bounds__(256, 8) void segment_chunks_kernel(const float* __r
                     pe[e] = p[i + e];
                     if (lazy_skip(z, i + e)) continue;
                     const float x = g[i + e];
-                    const bool f = finite(x);
+                    const bool f = finite_bits(x);
                     ge[e] = f ? x : 0.f;
                     a.nonfinite += f ? 0 : 1;
                     a.gmax = fmaxf(a.gmax, fabsf(ge[e]));
@@ -233,9 +220,9 @@ __global__ __launch_bounds__(256) void segment_finish_kernel(int segments, Scala
         if (threadIdx.x == 0) {
             head_i[slot * 4 + 0] = count;
             head_i[slot * 4 + 1] = sc.step_dev ? (int)*sc.step_dev : sc.step;
-            head_i[slot * 4 + 2] = (sc.skip && *sc.skip) ? 1 : 0;
+            head_i[slot * 4 + 2] = step_skipped(sc.skip) ? 1 : 0;
             head_i[slot * 4 + 3] = 1;
-            head_f[slot * 2 + 0] = sc.lr_dev ? *sc.lr_dev : sc.lr;
+            head_f[slot * 2 + 0] = device_wins(sc.lr_dev, sc.lr);
             head_f[slot * 2 + 1] = t.gsq;
         }
     }
@@ -273,21 +260,14 @@ extern "C" int mmvid_segment_stats(const float* g, const float* p, const float* 
     MMVID_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f, "segment_stats: beta1=%g or beta2=%g is outside [0, 1)",
                   (double)beta1, (double)beta2);  // (false for NaN)
     LazyRows z;
-    z.flags = nullptr, z.lo = z.hi = 0, z.rowlen = 1;
-    if (row_flags) {  // the conditions of csrc/optim.hip's make_lazy
-        MMVID_REQUIRE(table_lo >= 0 && table_rows >= 0 && rowlen > 0 && rowlen % 4 == 0 && table_lo % 4 == 0 && table_lo <= n &&
-                          table_rows <= (n - table_lo) / rowlen,
-                      "segment_stats: lazy rows: the table [%lld, +%lld x %d) must lie inside the buffer and be 4-element aligned",
-                      (long long)table_lo, (long long)table_rows, rowlen);
-        z.flags = row_flags, z.lo = table_lo, z.hi = table_lo + table_rows * rowlen, z.rowlen = rowlen;
-    }
+    if (int rc = make_lazy(z, "segment_stats", row_flags, table_lo, table_rows, rowlen, n)) return rc;
     if (n == 0) return MMVID_OK;
     Tables tb;
     tb.off = (const long*)seg_off, tb.len = (const long*)seg_len, tb.chunk0 = (const long*)seg_chunk0, tb.segments = segments, tb.chunks = chunks;
     Scalars sc;
     sc.lr = lr, sc.beta1 = beta1, sc.beta2 = beta2, sc.eps = eps, sc.step = step >= 1 ? step : 1;
-    sc.bc1 = 1.0f - powf(beta1, (float)sc.step);  // as adam_launch (csrc/optim.hip) computes them on the host
-    sc.bc2s = sqrtf(1.0f - powf(beta2, (float)sc.step));
+    const BiasCorrections bc = bias_corrections(beta1, beta2, (float)sc.step);
+    sc.bc1 = bc.bc1, sc.bc2s = bc.bc2_sqrt;
     sc.lr_dev = lr_dev, sc.step_dev = step_dev, sc.skip = (const int*)skip_dev;
     const unsigned blocks = (unsigned)(chunks < 2048 ? chunks : 2048);  // eight blocks per CU, all resident: see the head of this file
     hipLaunchKernelGGL(segment_chunks_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, p, m, v, (long)n, tb, sc, z,

@@ -124,11 +124,10 @@ class FlatTrainer:
         # shadow, allocated by the first `with ema_weights():`
         self.E = torch.zeros(tot, device=dev, dtype=torch.float32) if self.ema_decay is not None else None
         self.ES, self._ema_primed, self._ema_scope = None, False, False
-        for p, o in zip(self.params, offs):
-            n = p.numel()
-            self.P[o:o + n].copy_(p.detach().reshape(-1))
-            p.data = self.P[o:o + n].view(p.shape)
-            p.grad = self.G[o:o + n].view(p.shape)
+        self._index = {id(p): i for i, p in enumerate(self.params)}
+        for i, p in enumerate(self.params):
+            self._view(self.P, i).copy_(p.detach())
+            p.data, p.grad = self._view(self.P, i), self._view(self.G, i)
         self._attached = []  # the shadow.Bf16Weights that read views of S (_attach_shadows)
         if self.S is not None:
             ops.cast_bf16(self.P, self.S)
@@ -287,10 +286,13 @@ class FlatTrainer:
         z['dirty'][z['dirty_n']:z['dirty_n'] + n].copy_(ids)
         z['dirty_n'] += n
 
+    def _view(self, flat, i):
+        """Parameter i's view, in its own shape, of a flat buffer laid out like P."""
+        o, p = self.offsets[i], self.params[i]
+        return flat[o:o + p.numel()].view(p.shape)
+
     def _shadow_view(self, p, S=None):
-        i = next(k for k, q in enumerate(self.params) if q is p)
-        o = self.offsets[i]
-        return (self.S if S is None else S)[o:o + p.numel()].view(p.shape)
+        return self._view(self.S if S is None else S, self._index[id(p)])
 
     def _attach_shadows(self, S=None):
         """Every weight the MFMA kernels read in bf16 is a shadow.Bf16Weight, listed by the `bf16_weights()` of the module that owns
@@ -300,11 +302,10 @@ class FlatTrainer:
         records the parameter's data_ptr, so the parameters must already point where they will be read from.  The walk is over
         `model.modules()`: a model that only holds a tower (no `bf16_weights()` of its own) is served, and so is every tower
         registered anywhere below the model, not only `model.transformer`."""
-        flat = {id(p) for p in self.params}
         self._attached, self._tower_shadow_attached = [], False
         for mod in self.model.modules():
             for w in getattr(mod, 'bf16_weights', list)():
-                if id(w.param) in flat:
+                if id(w.param) in self._index:
                     w.attach(self._shadow_view(w.param, S))
                     self._attached.append(w)
                     self._tower_shadow_attached |= mod is getattr(self.model, 'transformer', None)  # (read by bench.py)
@@ -316,13 +317,13 @@ class FlatTrainer:
         `load_state_dict(assign=True)` or `.to()` would silently detach them.  Re-bind gradients, refuse moved params."""
         if self._ema_scope:
             raise RuntimeError('the model reads the averaged weights (inside `with trainer.ema_weights():`): leave the scope first')
-        for p, o in zip(self.params, self.offsets):
+        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
             if p.data_ptr() != self.P.data_ptr() + 4 * o:
                 raise RuntimeError('a parameter no longer lives in FlatTrainer.P (moved by .to() / load_state_dict(assign=True)); '
                                    'rebuild the trainer after moving the model')
             if p.grad is None or p.grad.data_ptr() != self.G.data_ptr() + 4 * o:
                 stray = p.grad
-                p.grad = self.G[o:o + p.numel()].view(p.shape)
+                p.grad = self._view(self.G, i)
                 if stray is not None:  # gradients were accumulated into a detached tensor this step: fold them in
                     p.grad.add_(stray)
                     if self._lazy is not None and o == self._lazy['lo']:
@@ -336,10 +337,9 @@ class FlatTrainer:
         non-finite guard the step count is first reconciled with the device (guard_stats): 'step' is the number of APPLIED steps."""
         guard = self.guard_stats() if self.guard_i is not None else None
         state = {}
-        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
-            n = p.numel()
-            state[i] = {'step': torch.tensor(float(self.step_count)), 'exp_avg': self.M[o:o + n].view(p.shape).clone(),
-                        'exp_avg_sq': self.V[o:o + n].view(p.shape).clone()}
+        for i in range(len(self.params)):
+            state[i] = {'step': torch.tensor(float(self.step_count)), 'exp_avg': self._view(self.M, i).clone(),
+                        'exp_avg_sq': self._view(self.V, i).clone()}
         group = {'lr': self.lr, 'betas': self.betas, 'eps': self.eps, 'weight_decay': self.wd, 'amsgrad': False,
                  'params': list(range(len(self.params)))}
         out = {'state': state, 'param_groups': [group], 'names': list(self.names)}
@@ -413,8 +413,8 @@ class FlatTrainer:
             live = (self.M[lo:hi].view(z['rows'], -1).abs().amax(1) > 0) | (self.V[lo:hi].view(z['rows'], -1).amax(1) > 0)
             z['flags'].copy_(live.to(torch.uint8) | z['flags'])
         if ema is not None:  # the averaged weights as saved; the decay and the warm-up stay the constructor's
-            for name, o, p in zip(self.names, self.offsets, self.params):
-                self.E[o:o + p.numel()].copy_(ema['weights'][name].reshape(-1))
+            for i, name in enumerate(self.names):
+                self._view(self.E, i).copy_(ema['weights'][name])
             self._ema_primed = True
             self._ema_flag_rows()
         elif self.E is not None:  # a checkpoint without averaged weights: E is primed again from the weights as they stand
@@ -476,7 +476,7 @@ class FlatTrainer:
         """{name: tensor} of the trainable parameters, taken from E (clones, parameter shapes): what
         `other_model.load_state_dict(..., strict=False)` takes to run another copy of the model on the averaged weights."""
         self._ema_prime()
-        return {n: self.E[o:o + p.numel()].view(p.shape).clone() for n, o, p in zip(self.names, self.offsets, self.params)}
+        return {n: self._view(self.E, i).clone() for i, n in enumerate(self.names)}
 
     def ema_weights(self):
         """`with trainer.ema_weights():` -- the model runs on the averaged weights inside the block (sampling, evaluation) and on the
@@ -713,24 +713,23 @@ class FlatTrainer:
                 lr_dev = self._lr_dev
             if self.guard_i is None:
                 ops.counter_add(self._step_dev, 1.0)
-        ops.grad_sqnorm(self.G, self._sq, partials=self._sq_partials, lazy=self._lazy_arg())
-        skip = None
+        # what Adam and the kernels after it on the stream read alike: the device's step count, the lazy rows, the guard's verdict
+        # (element 0 of guard_i; None: unguarded)
+        state = dict(step_dev=self._step_dev, lazy=self._lazy_arg(), skip_dev=self.guard_i)
+        ops.grad_sqnorm(self.G, self._sq, partials=self._sq_partials, lazy=state['lazy'])
         if self.guard_i is not None:
             # the verdict on the exchanged gradient, on the device: step_guard advances the step count in counter_add's place (only
             # where the step is applied) and Adam and the EMA return at once where it says skip -- no host input, so a replay obeys it
             ops.step_guard(self._sq, gscale, self._step_dev, self.guard_i, self.guard_f)
-            skip = self.guard_i  # (element 0)
         ops.adam_step(self.P, self.G, self.M, self.V, self.S, self.step_count, self.lr, self.betas, self.eps, self.wd,
-                      self.max_norm, self._sq, gscale, step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg(), skip_dev=skip)
-        if self._tel is not None:  # same stream, after Adam, with the scalars, the lazy rows and the verdict Adam got; it only reads
+                      self.max_norm, self._sq, gscale, lr_dev=lr_dev, **state)
+        if self._tel is not None:  # after Adam; it only reads
             t = self._tel
             ops.segment_stats(self.G, self.P, self.M, self.V, t['tables'], t['chunks'], self.step_count, self.lr, self.betas, self.eps,
                               self.telemetry_every, self.telemetry_slots, t['count'], t['partials_f'], t['partials_i'], t['ring_f'],
-                              t['ring_i'], t['head_i'], t['head_f'], step_dev=self._step_dev, lr_dev=lr_dev, lazy=self._lazy_arg(),
-                              skip_dev=skip)
-        if self.E is not None:  # same stream, after Adam; t is read from the device counter: a captured step carries it as it stands
-            ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, step_dev=self._step_dev, lazy=self._lazy_arg(),
-                           skip_dev=skip)
+                              t['ring_i'], t['head_i'], t['head_f'], lr_dev=lr_dev, **state)
+        if self.E is not None:  # after Adam; t is read from the device counter: a captured step carries it as it stands
+            ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, **state)
         for w in self._attached:
             # the Adam kernel wrote the attached bf16 views (a weight that is not attached is frozen: no kernel writes it); after a
             # skipped step they still equal cast(P)
@@ -761,8 +760,8 @@ class _EmaScope:
 
     def _point(self, flat, shadow):
         tr = self.tr
-        for p, o in zip(tr.params, tr.offsets):
-            p.data = flat[o:o + p.numel()].view(p.shape)
+        for i, p in enumerate(tr.params):
+            p.data = tr._view(flat, i)
         if shadow is not None:
             tr._attach_shadows(shadow)
 

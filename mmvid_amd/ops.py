@@ -458,15 +458,19 @@ def colsum_bf16(dy, db):
 
 
 # ------------------------------------------------------------------------------------------ optimiser
+def _lazy_args(lazy):
+    """lazy = (row_flags uint8 [rows], table_lo, rows, rowlen), or None for no table: the four arguments every entry takes for it."""
+    fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
+    return (None if fl is None else _p(_chk(fl, torch.uint8, 'row_flags'))), int(lo), int(rows), int(rowlen)
+
+
 def grad_sqnorm(g, out, partials=None, lazy=None):
     """out[0] += sum g^2.  With `partials` (fp32 [2048] scratch) the reduction order is fixed (deterministic).
-    lazy = (row_flags uint8 [rows], table_lo, rows, rowlen): skip the rows of that table whose flag is 0 (they are all-zero)."""
+    lazy (_lazy_args): skip the rows of that table whose flag is 0 (they are all-zero)."""
     _chk(g, f32, 'g'), _chk(out, f32, 'out')
     if lazy is not None:
         assert partials is not None
-        fl, lo, rows, rowlen = lazy
-        call('mmvid_grad_sqnorm_rows', _p(g), g.numel(), _p(partials), _p(out), _p(_chk(fl, torch.uint8, 'row_flags')), int(lo), int(rows),
-             int(rowlen), _stream())
+        call('mmvid_grad_sqnorm_rows', _p(g), g.numel(), _p(partials), _p(out), *_lazy_args(lazy), _stream())
     elif partials is not None:
         call('mmvid_grad_sqnorm_det', _p(g), g.numel(), _p(partials), _p(out), _stream())
     else:
@@ -479,10 +483,8 @@ def adam_step(p, g, m, v, shadow, step, lr, betas=(0.9, 0.999), eps=1e-8, weight
     (mmvid_adam_step_guarded).  None: the unguarded entry, as ever."""
     for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
         _chk(t, f32, n)
-    fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
     args = (_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), float(lr), _p(lr_dev), float(betas[0]), float(betas[1]), float(eps),
-            float(weight_decay), int(step), _p(step_dev), float(max_norm), _p(sqnorm), float(grad_scale), _p(fl), int(lo), int(rows),
-            int(rowlen))
+            float(weight_decay), int(step), _p(step_dev), float(max_norm), _p(sqnorm), float(grad_scale), *_lazy_args(lazy))
     if skip_dev is None:
         call('mmvid_adam_step_rows', *args, _stream())
     else:
@@ -496,8 +498,7 @@ def ema_update(ema, p, decay, warmup, step, step_dev=None, lazy=None, skip_dev=N
     _chk(ema, f32, 'ema'), _chk(p, f32, 'p')
     if ema.numel() != p.numel():
         raise ValueError(f'ema_update: ema has {ema.numel()} elements, p {p.numel()}')
-    fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
-    args = (_p(ema), _p(p), p.numel(), float(decay), int(bool(warmup)), int(step), _p(step_dev), _p(fl), int(lo), int(rows), int(rowlen))
+    args = (_p(ema), _p(p), p.numel(), float(decay), int(bool(warmup)), int(step), _p(step_dev), *_lazy_args(lazy))
     if skip_dev is None:
         call('mmvid_ema_update', *args, _stream())
     else:
@@ -542,11 +543,10 @@ def segment_stats(g, p, m, v, tables, chunks, step, lr, betas, eps, every, slots
     if (partials_f.numel() < 4 * chunks or partials_i.numel() < 2 * chunks or ring_f.numel() != slots * S * 4 or ring_i.numel() != slots * S * 2
             or head_i.numel() != slots * 4 or head_f.numel() != slots * 2 or count.numel() < 1):
         raise ValueError(f'segment_stats: buffers do not fit {S} segments, {chunks} chunks and {slots} slots')
-    fl, lo, rows, rowlen = lazy if lazy is not None else (None, 0, 0, 0)
     if skip_dev is not None:
         _chk(skip_dev, torch.int32, 'skip_dev')
     call('mmvid_segment_stats', _p(g), _p(p), _p(m), _p(v), p.numel(), _p(off), _p(ln), _p(c0), S, int(chunks), float(lr), _p(lr_dev),
-         float(betas[0]), float(betas[1]), float(eps), int(step), _p(step_dev), _p(fl), int(lo), int(rows), int(rowlen), _p(skip_dev),
+         float(betas[0]), float(betas[1]), float(eps), int(step), _p(step_dev), *_lazy_args(lazy), _p(skip_dev),
          int(every), int(slots), _p(count), _p(partials_f), _p(partials_i), _p(ring_f), _p(ring_i), _p(head_i), _p(head_f), _stream())
 
 

@@ -67,7 +67,8 @@ def test_guard_entry_points_refuse_bad_arguments_without_a_launch():
     for kw, word in ((dict(skip=V((5 << 20) + 2)), 'skip_dev'), (dict(skip=V((5 << 20) + 1)), 'skip_dev'), (dict(p=None), 'bad arguments'),
                      (dict(g=None), 'bad arguments'), (dict(n=-1), 'bad arguments'), (dict(step=0), 'bad arguments'),
                      (dict(p=V((1 << 20) + 4)), 'aligned'), (dict(flags=f, lo=8, rows=5, rowlen=12, wd=0.1), 'weight decay'),
-                     (dict(flags=f, lo=8, rows=5, rowlen=10), 'lazy'), (dict(flags=f, lo=8, rows=5, rowlen=12, n=67), 'lazy')):
+                     (dict(flags=f, lo=8, rows=5, rowlen=10), 'lazy'), (dict(flags=f, lo=8, rows=5, rowlen=12, n=67), 'lazy'),
+                     (dict(flags=f, lo=0, rows=1 << 62, rowlen=4), 'lazy')):  # (the last: rows * rowlen wraps to 0)
         with pytest.raises(_lib.MMVIDError, match=word):
             adam(**kw)
     adam(n=0)  # nothing to update: no launch, no error
@@ -78,7 +79,8 @@ def test_guard_entry_points_refuse_bad_arguments_without_a_launch():
 
     for kw, word in ((dict(skip=V((5 << 20) + 2)), 'skip_dev'), (dict(ema_=None), 'NULL'), (dict(p=None), 'NULL'), (dict(p=a), 'overlap'),
                      (dict(n=-1), 'negative'), (dict(ema_=V((1 << 20) + 4)), 'aligned'), (dict(decay=1.0), 'decay'),
-                     (dict(decay=float('nan')), 'decay'), (dict(step=0), 'step'), (dict(flags=f, lo=6, rows=5, rowlen=12), 'lazy')):
+                     (dict(decay=float('nan')), 'decay'), (dict(step=0), 'step'), (dict(flags=f, lo=6, rows=5, rowlen=12), 'lazy'),
+                     (dict(flags=f, lo=0, rows=1 << 62, rowlen=4), 'lazy')):
         with pytest.raises(_lib.MMVIDError, match=word):
             ema(**kw)
     ema(n=0)

@@ -468,6 +468,7 @@ def test_adam_argument_contract():
         'table_lo % 4 != 0': dict(flags=F, lo=6, rows=8, rowlen=8),
         'rowlen % 4 != 0': dict(flags=F, lo=0, rows=8, rowlen=6),
         'a table reaching past n': dict(flags=F, lo=n - 60, rows=8, rowlen=8),
+        'a table whose rows * rowlen wraps to a size that fits': dict(flags=F, lo=n - 64, rows=(1 << 62) + 8, rowlen=8),
         'step < 1 without step_dev': dict(step=0),
     })
     for what, kw in bad.items():
