@@ -140,8 +140,7 @@ CENSUS = {
     ('frontend.hip', 'token_rows_gather_kernel'): (1, EXACT, 'fault counter, unsigned long long'),
     ('gemm.hip', 'gemm_epilogue'): (2, DET, 'mmvid_gemm_bf16_det: split-K through slabs, column sums through colsum_det'),
     ('gemm.hip', 'colsum_wave'): (1, DET, 'mmvid_gemm_bf16_det: colsum_det stores to the slab'),
-    ('norm.hip', 'layernorm_bwd_kernel'): (3, DET, 'the workspace form (mmvid_layernorm_bwd_ws); the mode refuses this branch'),
-    ('norm.hip', 'layernorm_bwd_fast_kernel'): (3, DET, 'the workspace form (mmvid_layernorm_bwd_ws); the mode refuses this branch'),
+    ('norm.hip', 'ln_bwd_block_sums'): (3, DET, 'the workspace form (mmvid_layernorm_bwd_ws); the mode refuses this branch'),
     ('optim.hip', 'grad_sqnorm_kernel'): (1, DET, 'mmvid_grad_sqnorm_det, the only form the engine calls'),
     ('sample.hip', 'mp_select_keep_kernel'): (2, EXACT, 'int counts of the mask-predict sampler; ' + OFF),
 }
