@@ -194,6 +194,59 @@ int mmvid_segment_stats(const float* g, const float* p, const float* m, const fl
                         int32_t every, int32_t slots, int32_t* count_dev, float* partials_f, int32_t* partials_i,
                         float* ring_f, int32_t* ring_i, int32_t* head_i, float* head_f, void* stream);
 
+/* ---- AdamW and the learning-rate schedules of --lr_scheduler, on the device -------------------------------------------------------
+ *
+ * mmvid_adam_step_decoupled is torch.optim.AdamW (utils/utils_train.py:173-179, `--optimizer adamw`; stepped at train.py:324-325):
+ * the argument list of mmvid_adam_step_guarded (skip_dev may be NULL), and with coef, bc1, bc2s, the step count and the learning rate
+ * formed exactly as in every other Adam entry (csrc/optim.hip: one kernel text, this form a compile-time variant of it)
+ *     gr   = g * coef                                            no decay term in the gradient
+ *     m'   = b1 m + (1 - b1) gr ;  v' = b2 v + (1 - b2) gr^2
+ *     keep = 1.f - lr * wd                                       one fp32 scalar per launch; lr is *lr_dev where lr_dev != NULL
+ *     p'   = p * keep - (lr / bc1) * m' / (sqrtf(v') / bc2s + eps)
+ * which is AdamW's order (param.mul_(1 - lr * wd) first).  tests/adamw_ref.py is the fp64 replica with its derived bound.  The bf16
+ * shadow, the lazy rows and the verdict behave as in mmvid_adam_step_guarded; with weight_decay == 0 the bytes written are that
+ * entry's.  Refused (nothing launched): everything mmvid_adam_step_guarded refuses -- a lazy table with weight_decay != 0 included: a
+ * row that never saw a gradient still decays --, and a weight_decay that is negative or not finite.  No atomics. */
+int mmvid_adam_step_decoupled(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, const float* lr_dev,
+                              float beta1, float beta2, float eps, float weight_decay, int step, const float* step_dev, float max_norm,
+                              const float* sqnorm, float grad_scale, const uint8_t* row_flags, int64_t table_lo, int64_t table_rows,
+                              int rowlen, const int32_t* skip_dev, void* stream);
+
+/* mmvid_lr_schedule_ext: the closed-form schedules of utils/utils_train.py:332-371 beside mmvid_lr_schedule's kinds 0 and 1, one
+ * thread, *lr_out written from *step_dev (the fp32 count of finished optimiser steps).  ns = (long)*step_dev / every is the number of
+ * scheduler steps taken before this iteration (train.py:373-374 steps the scheduler after every `every`-th iteration).
+ *     kind 2  StepLR(step_size = a, gamma)  (utils_train.py:332-343)
+ *                 lr = lr_max * powf(gamma, (float)(ns / a))                                    integer quotient
+ *     kind 3  CosineAnnealingLR(T_max = a, eta_min = lr_min)  (utils_train.py:345-356)
+ *                 r = ns % (2 a) ;  x = (PI * (float)r) / (float)a ;  lr = lr_min + ((lr_max - lr_min) * (1.f + cosf(x))) * 0.5f
+ *                 PI the fp32 nearest to pi.  The argument is reduced in integers: the error does not grow with the step count.
+ *     kind 4  deepspeed WarmupDecayLR(total = b, min = lr_min, max = lr_max, warmup = a)  (utils_train.py:358-371)
+ *                 ns == 0: lr_max (the optimiser's construction rate).  Otherwise k = ns - 1, w = max(a, 2),
+ *                 g = k < w ? logf((float)(k + 1)) / logf((float)w) : fmaxf(0.f, (float)(b - k) / (float)max(1, b - w))
+ *                 lr = lr_min + (lr_max - lr_min) * g
+ *                 The warm-up branch and the clamp w >= 2 are kind 1's.  Third-party arithmetic, restated from deepspeed's
+ *                 published semantics: parity unpinned, as for kind 1.
+ * Every product, sum and quotient is one rounded fp32 operation; powf, cosf and logf are the device library's.  lr_min is not read by
+ * kind 2, gamma only by kind 2, b only by kind 4.  Refused (nothing launched): a NULL or misaligned pointer; kind outside 2..4 (0 and
+ * 1 stay with mmvid_lr_schedule); every < 1; a < 1; b < a for kind 4; gamma outside (0, 1] or NaN for kind 2; a (kind 4: b) above
+ * 2^24, where the fp32 step count stops -- below it every integer the kernel converts is exact. */
+int mmvid_lr_schedule_ext(const float* step_dev, int kind, float lr_min, float lr_max, int every, int64_t a, int64_t b, float gamma,
+                          float* lr_out, void* stream);
+
+/* mmvid_lr_plateau: torch's ReduceLROnPlateau(mode='min', threshold_mode='rel') (utils/utils_train.py:315-330, fed the loss at
+ * train.py:373-374) as one device thread.  state_f = {lr, best} (fp32 [2]; best starts at +inf; state_f is what the Adam entries take
+ * as lr_dev), state_i = {bad epochs, cool-down left, reductions} (int32 [3]), loss_dev an fp32 on the device.  Launched AFTER the
+ * optimiser, *step_dev already advanced.  Returns at once where skip_dev != NULL and *skip_dev != 0 (the step was skipped) or where
+ * (long)*step_dev % every != 0.  Otherwise, in fp32, each operation rounded once, in this order:
+ *     if (loss < best * (1.f - threshold)) { best = loss; bad = 0; } else bad += 1;          NaN compares false: a bad epoch
+ *     if (cool > 0) { cool -= 1; bad = 0; }
+ *     if (bad > patience) { nw = fmaxf(lr * factor, min_lr); if (lr - nw > eps) { lr = nw; reductions += 1; } cool = cooldown; bad = 0; }
+ * Multiplies, subtractions and comparisons only: tests/sched_ref.py replays it bit for bit.  Refused (nothing launched): a NULL
+ * loss_dev, step_dev, state_f or state_i; a pointer that is not 4-byte aligned; every < 1; factor outside (0, 1); patience or
+ * cooldown < 0; threshold outside [0, 1); min_lr or eps negative or not finite.  No atomics. */
+int mmvid_lr_plateau(const float* loss_dev, const float* step_dev, int every, float factor, int patience, int cooldown, float threshold,
+                     float min_lr, float eps, float* state_f, int32_t* state_i, const int32_t* skip_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 #include "../../include/mmvid_hip.h"
 #include "common.h"
 #include "philox.h"
+#include "step_state.h"
 
 namespace {
 
@@ -515,8 +516,8 @@ __global__ void lr_schedule_kernel(const float* __restrict__ step_dev, int kind,
         const long ns = it / (every > 0 ? every : 1);
         if (ns > 0) {
             const long k = ns - 1;
-            const int wu = warmup < 2 ? 2 : warmup;
-            const float gamma = k < wu ? logf((float)(k + 1)) / logf((float)wu) : 1.0f;
+            const long wu = warmup_clamped(warmup);
+            const float gamma = k < wu ? warmup_log_gamma(k, wu) : 1.0f;  // (step_state.h: shared with mmvid_lr_schedule_ext)
             lr = lr_min + (lr_max - lr_min) * gamma;
         }
     }

@@ -47,5 +47,13 @@ __host__ __device__ __forceinline__ BiasCorrections bias_corrections(float beta1
     return {1.0f - powf(beta1, t), sqrtf(1.0f - powf(beta2, t))};
 }
 
+// The warm-up of deepspeed's WarmupLR and WarmupDecayLR (third-party: restated from its published semantics) after k scheduler
+// steps, k < warmup: log(k + 1) / log(warmup), the warm-up length clamped to >= 2 as deepspeed clamps it.  Kind 1 of
+// mmvid_lr_schedule and kind 4 of mmvid_lr_schedule_ext both take it from here.
+__device__ __forceinline__ long warmup_clamped(long warmup) { return warmup < 2 ? 2 : warmup; }
+__device__ __forceinline__ float warmup_log_gamma(long k, long warmup_clamped_) {
+    return logf((float)(k + 1)) / logf((float)warmup_clamped_);
+}
+
 // a float4 of a buffer that is read once per step
 __device__ __forceinline__ f32x4 load_once(const float* q) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)); }

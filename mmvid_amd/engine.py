@@ -47,6 +47,168 @@ class WarmupLR:
         return self.min_lr + (self.max_lr - self.min_lr) * gamma
 
 
+def _positive_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f'{name}={v!r}: an int >= 1')
+    return v
+
+
+def _finite(name, v, lo=0.0):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) < float('inf'):  # (NaN: False)
+        raise ValueError(f'{name}={v!r}: a finite number >= {lo}')
+    return float(v)
+
+
+class _ClosedFormLR:
+    """A schedule mmvid_lr_schedule_ext evaluates from the device step count alone: no state, so a resumed or captured step follows
+    it from the restored count.  ns = iteration // every scheduler steps have happened before `iteration` (train.py:373-374).
+    `lr_at(i)` is the host view in fp64; `ext_args()` the (kind, lr_min, lr_max, every, a, b, gamma) of the device call."""
+
+    def ns(self, iteration):
+        return int(iteration) // self.every
+
+
+class StepLR(_ClosedFormLR):
+    """torch.optim.lr_scheduler.StepLR(step_size, gamma) as the reference builds it (utils_train.py:332-343: gamma 0.5)."""
+
+    def __init__(self, lr, step_size, gamma=0.5, every=1):
+        self.lr, self.step_size, self.every = _finite('lr', lr), _positive_int('step_size', step_size), _positive_int('every', every)
+        self.gamma = _finite('gamma', gamma)
+        if not 0.0 < self.gamma <= 1.0:
+            raise ValueError(f'gamma={gamma!r}: in (0, 1]')
+
+    def lr_at(self, iteration):
+        return self.lr * self.gamma**(self.ns(iteration) // self.step_size)
+
+    def ext_args(self):
+        return ops.LR_STEP, 0.0, self.lr, self.every, self.step_size, 0, self.gamma
+
+
+class CosineAnnealingLR(_ClosedFormLR):
+    """torch.optim.lr_scheduler.CosineAnnealingLR(T_max, eta_min) as the reference builds it (utils_train.py:345-356: eta_min 1e-6),
+    in its closed form with the argument reduced in integers: r = ns mod 2 T_max, eta_min + (lr - eta_min) (1 + cos(pi r / T_max)) / 2.
+    torch steps a recursion whose value drifts from this by rounding only (tests/test_sched_host.py)."""
+
+    def __init__(self, lr, T_max, eta_min=1e-6, every=1):
+        self.lr, self.T_max, self.every = _finite('lr', lr), _positive_int('T_max', T_max), _positive_int('every', every)
+        self.eta_min = _finite('eta_min', eta_min)
+
+    def lr_at(self, iteration):
+        import math
+        r = self.ns(iteration) % (2 * self.T_max)
+        return self.eta_min + (self.lr - self.eta_min) * (1.0 + math.cos(math.pi * r / self.T_max)) / 2.0
+
+    def ext_args(self):
+        return ops.LR_COSINE, self.eta_min, self.lr, self.every, self.T_max, 0, 1.0
+
+
+class WarmupDecayLR(_ClosedFormLR):
+    """deepspeed.runtime.lr_schedules.WarmupDecayLR as the reference builds it (utils_train.py:358-371; third-party, restated from
+    its published semantics: parity unpinned, as for WarmupLR): WarmupLR's logarithmic warm-up, then a linear decay that reaches
+    warmup_min_lr at scheduler step total_num_steps, gamma = max(0, (total - k) / max(1, total - warmup)).  Before the first
+    scheduler step the optimiser runs at its construction lr, warmup_max_lr."""
+
+    def __init__(self, total_num_steps, warmup_min_lr=1e-6, warmup_max_lr=1e-4, warmup_num_steps=1000, every=1):
+        self.min_lr, self.max_lr = _finite('warmup_min_lr', warmup_min_lr), _finite('warmup_max_lr', warmup_max_lr)
+        self.warmup_arg = _positive_int('warmup_num_steps', warmup_num_steps)
+        self.warmup = max(2, self.warmup_arg)
+        self.total, self.every = _positive_int('total_num_steps', total_num_steps), _positive_int('every', every)
+        if self.total < self.warmup_arg:
+            raise ValueError(f'total_num_steps={total_num_steps} is below warmup_num_steps={warmup_num_steps}')
+
+    def lr_at(self, iteration):
+        import math
+        ns = self.ns(iteration)
+        if ns == 0:
+            return self.max_lr
+        k = ns - 1
+        if k < self.warmup:
+            gamma = math.log(k + 1) / math.log(self.warmup)
+        else:
+            gamma = max(0.0, (self.total - k) / max(1, self.total - self.warmup))
+        return self.min_lr + (self.max_lr - self.min_lr) * gamma
+
+    def ext_args(self):
+        return ops.LR_WARMUP_DECAY, self.min_lr, self.max_lr, self.every, self.warmup_arg, self.total, 1.0
+
+
+class ReduceLROnPlateau:
+    """torch.optim.lr_scheduler.ReduceLROnPlateau(mode='min', threshold_mode='rel') as the reference builds it (utils_train.py:315-330:
+    factor 0.5, patience 2, cooldown 5, min_lr 1e-6; threshold 1e-4 and eps 1e-8 are torch's defaults), fed the loss of every
+    `every`-th iteration (train.py:373-374).  The trainer keeps its state on the device (mmvid_lr_plateau) and steps it from the loss
+    tensor given to `FlatTrainer.step(loss=...)`; `replay(losses)` is the host view of the same fp32 rule."""
+    STATE = ('lr', 'best', 'bad', 'cooldown', 'reductions')
+
+    def __init__(self, lr, factor=0.5, patience=2, cooldown=5, min_lr=1e-6, threshold=1e-4, eps=1e-8, every=1):
+        self.lr, self.min_lr, self.eps = _finite('lr', lr), _finite('min_lr', min_lr), _finite('eps', eps)
+        self.factor, self.threshold = _finite('factor', factor), _finite('threshold', threshold)
+        if not 0.0 < self.factor < 1.0:
+            raise ValueError(f'factor={factor!r}: in (0, 1)')
+        if not self.threshold < 1.0:
+            raise ValueError(f'threshold={threshold!r}: in [0, 1)')
+        for name, v in (('patience', patience), ('cooldown', cooldown)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f'{name}={v!r}: an int >= 0')
+        self.patience, self.cooldown, self.every = patience, cooldown, _positive_int('every', every)
+
+    def initial_state(self):
+        """(state_f, state_i) as the device holds them before the first scheduler step."""
+        return [self.lr, float('inf')], [0, 0, 0]
+
+    def replay(self, losses, state=None):
+        """The learning rate after each scheduler step fed `losses` in turn, from `state` (default: initial_state()), in the fp32
+        arithmetic of the device -> (list of lr, final (state_f, state_i))."""
+        import numpy as np
+        f = np.float32
+        sf, si = state if state is not None else self.initial_state()
+        lr, best = f(sf[0]), f(sf[1])
+        bad, cool, reductions = (int(x) for x in si)
+        keep, out = f(1) - f(self.threshold), []
+        with np.errstate(invalid='ignore', over='ignore'):
+            for loss in losses:
+                loss = f(loss)
+                if loss < best * keep:
+                    best, bad = loss, 0
+                else:
+                    bad += 1
+                if cool > 0:
+                    cool, bad = cool - 1, 0
+                if bad > self.patience:
+                    nw = max(lr * f(self.factor), f(self.min_lr))
+                    if lr - nw > f(self.eps):
+                        lr, reductions = nw, reductions + 1
+                    cool, bad = self.cooldown, 0
+                out.append(float(lr))
+        return out, ([float(lr), float(best)], [bad, cool, reductions])
+
+
+def lr_scheduler_from_args(name, learning_rate, iters=None, step_size=None, warmup=None, every=1):
+    """The reference's prepare_lr_scheduler (utils_train.py:314-388) with its constants: `name` is --lr_scheduler, `learning_rate`
+    --learning_rate, `iters` --iters, `step_size` --lr_scheduler_step_size, `warmup` --lr_scheduler_warmup, `every`
+    --lr_scheduler_every.  -> the schedule object for FlatTrainer(lr_schedule=...)."""
+    if name == 'reducelronplateau':
+        return ReduceLROnPlateau(learning_rate, factor=0.5, patience=2, cooldown=5, min_lr=1e-6, every=every)
+    if name == 'steplr':
+        return StepLR(learning_rate, step_size, gamma=0.5, every=every)
+    if name == 'cosineannealinglr':
+        return CosineAnnealingLR(learning_rate, step_size, eta_min=1e-6, every=every)
+    if name == 'warmupdecaylr':
+        return WarmupDecayLR(iters, 1e-6, learning_rate, warmup, every=every)
+    if name == 'warmuplr':
+        return WarmupLR(1e-6, learning_rate, warmup, every=every)
+    raise NotImplementedError(f'lr_scheduler {name!r}')
+
+
+def optimizer_kwargs(name, weight_decay=0.0):
+    """The reference's get_optimizer (utils_train.py:167-182) as FlatTrainer keywords: 'adam' is torch.optim.Adam with its default
+    betas and L2 decay, 'adamw' torch.optim.AdamW with betas (0.9, 0.95) and decoupled decay."""
+    if name == 'adam':
+        return dict(betas=(0.9, 0.999), weight_decay=weight_decay, decoupled_weight_decay=False)
+    if name == 'adamw':
+        return dict(betas=(0.9, 0.95), weight_decay=weight_decay, decoupled_weight_decay=True)
+    raise NotImplementedError(f'optimizer {name!r}')
+
+
 PROVEN_TOWER_WIDTH = 768  # the widest tower whose captured / deterministic trainer step is covered by passing tests
 
 
@@ -73,8 +235,24 @@ class FlatTrainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0,
                  process_group=None, bucket_mb=64, order=None, lr_schedule=None, force_exchange=False, sparse_tables=True,
                  lazy_rows=True, exchange=None, ema_decay=None, ema_warmup=False, skip_nonfinite=False,
-                 telemetry_every=None, telemetry_slots=64):
+                 telemetry_every=None, telemetry_slots=64, decoupled_weight_decay=False):
         self.model = model
+        # AdamW and the schedules of --lr_scheduler (INTEGRATION.md "Optimiser and schedule flags"): False and a WarmupLR (or None) = the
+        # launches and the state_dict() of a trainer built without these keywords
+        if not isinstance(decoupled_weight_decay, bool):
+            raise ValueError(f'decoupled_weight_decay={decoupled_weight_decay!r}: True or False')
+        if isinstance(weight_decay, bool) or not isinstance(weight_decay, (int, float)) or not 0.0 <= float(weight_decay) < float('inf'):
+            raise ValueError(f'weight_decay={weight_decay!r}: a finite number >= 0 (a negative decay grows the weights)')
+        if decoupled_weight_decay and weight_decay != 0 and telemetry_every is not None:
+            raise ValueError('decoupled_weight_decay=True with weight_decay != 0 and telemetry_every: the telemetry restates the update '
+                             'from the moments Adam left (mmvid_segment_stats) and would miss the decay term p * lr * weight_decay')
+        self.decoupled = decoupled_weight_decay
+        if isinstance(lr_schedule, ReduceLROnPlateau):
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
+                raise ValueError('a ReduceLROnPlateau schedule in a process group of more than one rank: the reference feeds each rank its '
+                                 'own loss (train.py:327, 374), so the ranks\' learning rates drift apart; that is not reproduced')
+            if any(p.requires_grad and p.device.type != 'cuda' for p in model.parameters()):
+                raise ValueError('a ReduceLROnPlateau schedule on a host trainer: its state lives on the device and is stepped by a kernel')
         # trainer telemetry (INTEGRATION.md "Trainer telemetry"): None = off -- no buffer, no launch, state_dict() unchanged key for key
         for key, val in (('telemetry_every', telemetry_every), ('telemetry_slots', telemetry_slots)):
             if (val is not None or key == 'telemetry_slots') and (isinstance(val, bool) or not isinstance(val, int) or val < 1):
@@ -143,6 +321,13 @@ class FlatTrainer:
         # the right Adam bias corrections and learning rate without the host passing new scalars
         self._step_dev = torch.zeros(1, device=dev, dtype=torch.float32) if dev.type == 'cuda' else None
         self._lr_dev = torch.full((1, ), float(lr), device=dev, dtype=torch.float32) if dev.type == 'cuda' else None
+        # the plateau schedule's device state (mmvid_lr_plateau): plateau_f = lr, best -- element 0 is the lr_dev Adam reads --,
+        # plateau_i = bad epochs, cool-down left, reductions
+        self.plateau_f = self.plateau_i = None
+        if isinstance(lr_schedule, ReduceLROnPlateau):
+            sf, si = lr_schedule.initial_state()
+            self.plateau_f = torch.tensor(sf, dtype=torch.float32).to(dev)
+            self.plateau_i = torch.tensor(si, dtype=torch.int32).to(dev)
         # the guard's device state (mmvid_step_guard): guard_i = verdict, steps skipped, current run of skips, steps seen;
         # guard_f = gradient norm of the last step, last finite gradient norm.  A host trainer has no optimiser kernel to guard.
         guarded = self.skip_nonfinite and dev.type == 'cuda'
@@ -342,7 +527,11 @@ class FlatTrainer:
                         'exp_avg_sq': self._view(self.V, i).clone()}
         group = {'lr': self.lr, 'betas': self.betas, 'eps': self.eps, 'weight_decay': self.wd, 'amsgrad': False,
                  'params': list(range(len(self.params)))}
+        if self.decoupled:  # (the key torch.optim.AdamW's own state_dict() carries: a reference `adamw` checkpoint has it too)
+            group['decoupled_weight_decay'] = True
         out = {'state': state, 'param_groups': [group], 'names': list(self.names)}
+        if self.plateau_f is not None:  # (one device read each; the closed-form schedules follow the step count and keep no state)
+            out['lr_plateau'] = dict(zip(ReduceLROnPlateau.STATE, self.plateau_f.tolist() + self.plateau_i.tolist()))
         fe = getattr(self.model, 'frontend', None)
         if fe is not None and hasattr(fe, 'state_dict'):
             out['frontend'] = fe.state_dict()
@@ -357,6 +546,10 @@ class FlatTrainer:
         train.py:352): without a 'names' entry the indices are torch's -- position in the requires_grad-filtered
         `model.parameters()` order the reference hands to Adam (utils_train.py:167-172) -- and are mapped through the
         parameter names to the flat layout; every entry's shape is checked, so moments can never land on another layer."""
+        saved_decoupled = bool(sd['param_groups'][0].get('decoupled_weight_decay', False))
+        if saved_decoupled != self.decoupled:
+            raise ValueError(f'the optimiser state was saved with decoupled_weight_decay={saved_decoupled} (AdamW: True, Adam: False) and '
+                             f'this trainer was built with decoupled_weight_decay={self.decoupled}: the moments would be stepped by the other rule')
         if 'names' in sd:
             names = list(sd['names'])
         else:
@@ -402,6 +595,13 @@ class FlatTrainer:
         if self._tel is not None:  # the ring is diagnostics, not state: a resumed trainer starts with an empty one
             self._tel['head_i'].zero_()
             self._tel['count'].zero_()
+        if self.plateau_f is not None:  # the five values as saved; none saved: the schedule starts again
+            saved = sd.get('lr_plateau')
+            sf, si = self.lr_schedule.initial_state()
+            if saved is not None:
+                sf, si = [saved['lr'], saved['best']], [saved['bad'], saved['cooldown'], saved['reductions']]
+            self.plateau_f.copy_(torch.tensor(sf, dtype=torch.float32))
+            self.plateau_i.copy_(torch.tensor([int(x) for x in si], dtype=torch.int32))
         g = sd['param_groups'][0]
         self.lr, self.betas, self.eps, self.wd = g['lr'], tuple(g['betas']), g['eps'], g['weight_decay']
         fe = getattr(self.model, 'frontend', None)
@@ -682,10 +882,19 @@ class FlatTrainer:
                 torch.cuda.current_stream().wait_stream(self._comm_stream)
         self._sent_from = self.numel
 
-    def step(self):
-        """clip_grad_norm_(max_norm) + Adam (train.py:324-325) on the averaged gradients."""
+    def step(self, loss=None):
+        """clip_grad_norm_(max_norm) + Adam (train.py:324-325) on the averaged gradients.  loss: what a ReduceLROnPlateau schedule is
+        stepped with (train.py:373-374) -- a one-element fp32 tensor on the trainer's device, read by the device; no other schedule
+        looks at it."""
         if self._ema_scope:
             raise RuntimeError('step() inside `with trainer.ema_weights():`: the model reads the averaged weights; leave the scope first')
+        if self.plateau_f is not None:
+            if not (isinstance(loss, torch.Tensor) and loss.numel() == 1 and loss.dtype == torch.float32 and loss.device == self.P.device
+                    and loss.is_contiguous()):
+                raise ValueError('a ReduceLROnPlateau schedule needs step(loss=...): a one-element fp32 tensor on the trainer\'s device '
+                                 '(the device steps the schedule from it), got '
+                                 f'{(loss.dtype, loss.device, tuple(loss.shape)) if isinstance(loss, torch.Tensor) else repr(loss)}')
+            loss = loss.detach()
         if _lib.is_deterministic():
             refuse_unproven_width(self.model, 'a deterministic-mode trainer step')
         self._check_bindings()
@@ -707,8 +916,14 @@ class FlatTrainer:
         self._sq.zero_()
         lr_dev = None
         if self._step_dev is not None:
-            if self.lr_schedule is not None:  # lr of THIS iteration from the count of finished steps, on the device
-                sc = self.lr_schedule
+            sc = self.lr_schedule
+            if self.plateau_f is not None:  # the rate the last scheduler step left; this iteration's scheduler step follows Adam
+                lr_dev = self.plateau_f
+            elif isinstance(sc, _ClosedFormLR):
+                kind, lo, hi, every, a, b, gamma = sc.ext_args()
+                ops.lr_schedule_ext(self._step_dev, kind, lo, hi, every, a, b, gamma, self._lr_dev)
+                lr_dev = self._lr_dev
+            elif sc is not None:  # lr of THIS iteration from the count of finished steps, on the device
                 ops.lr_schedule(self._step_dev, 1, sc.min_lr, sc.max_lr, sc.warmup, sc.every, self._lr_dev)
                 lr_dev = self._lr_dev
             if self.guard_i is None:
@@ -722,7 +937,7 @@ class FlatTrainer:
             # where the step is applied) and Adam and the EMA return at once where it says skip -- no host input, so a replay obeys it
             ops.step_guard(self._sq, gscale, self._step_dev, self.guard_i, self.guard_f)
         ops.adam_step(self.P, self.G, self.M, self.V, self.S, self.step_count, self.lr, self.betas, self.eps, self.wd,
-                      self.max_norm, self._sq, gscale, lr_dev=lr_dev, **state)
+                      self.max_norm, self._sq, gscale, lr_dev=lr_dev, decoupled=self.decoupled, **state)
         if self._tel is not None:  # after Adam; it only reads
             t = self._tel
             ops.segment_stats(self.G, self.P, self.M, self.V, t['tables'], t['chunks'], self.step_count, self.lr, self.betas, self.eps,
@@ -730,6 +945,12 @@ class FlatTrainer:
                               t['ring_i'], t['head_i'], t['head_f'], lr_dev=lr_dev, **state)
         if self.E is not None:  # after Adam; t is read from the device counter: a captured step carries it as it stands
             ops.ema_update(self.E, self.P, self.ema_decay, self.ema_warmup, self.step_count, **state)
+        if self.plateau_f is not None:
+            # the scheduler step of train.py:373-374, after everything that reads the learning rate of THIS step; it does nothing where
+            # the guard skipped the step or the (already advanced) step count is no multiple of `every`
+            sc = self.lr_schedule
+            ops.lr_plateau(loss.reshape(1), self._step_dev, sc.every, sc.factor, sc.patience, sc.cooldown, sc.threshold, sc.min_lr, sc.eps,
+                           self.plateau_f, self.plateau_i, skip_dev=self.guard_i)
         for w in self._attached:
             # the Adam kernel wrote the attached bf16 views (a weight that is not attached is frozen: no kernel writes it); after a
             # skipped step they still equal cast(P)
@@ -866,7 +1087,10 @@ class GraphedStep:
         self.trainer.zero_grad()
         loss = self.fn(**self.static)
         loss.backward()
-        self.trainer.step()
+        if isinstance(self.trainer.lr_schedule, ReduceLROnPlateau):  # the plateau schedule is stepped on the device from this step's loss
+            self.trainer.step(loss=loss.detach())
+        else:
+            self.trainer.step()
         return loss.detach()
 
     def __call__(self, **inputs):

@@ -478,14 +478,19 @@ def grad_sqnorm(g, out, partials=None, lazy=None):
 
 
 def adam_step(p, g, m, v, shadow, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=0.0,
-              sqnorm=None, grad_scale=1.0, step_dev=None, lr_dev=None, lazy=None, skip_dev=None):
+              sqnorm=None, grad_scale=1.0, step_dev=None, lr_dev=None, lazy=None, skip_dev=None, decoupled=False):
     """skip_dev: the verdict of step_guard (int32 on the device) -- where it is non-zero at execution the kernel writes nothing
-    (mmvid_adam_step_guarded).  None: the unguarded entry, as ever."""
+    (mmvid_adam_step_guarded).  None: the unguarded entry, as ever.  decoupled: torch.optim.AdamW's rule -- the decay scales the
+    weight by 1 - lr * weight_decay and stays out of the gradient (mmvid_adam_step_decoupled; skip_dev may be None)."""
     for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
         _chk(t, f32, n)
     args = (_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), float(lr), _p(lr_dev), float(betas[0]), float(betas[1]), float(eps),
             float(weight_decay), int(step), _p(step_dev), float(max_norm), _p(sqnorm), float(grad_scale), *_lazy_args(lazy))
-    if skip_dev is None:
+    if decoupled:
+        if not 0.0 <= float(weight_decay) < float('inf'):  # (NaN: False)
+            raise ValueError(f'adam_step: decoupled weight_decay={weight_decay!r} must be finite and >= 0')
+        call('mmvid_adam_step_decoupled', *args, None if skip_dev is None else _p(_chk(skip_dev, torch.int32, 'skip_dev')), _stream())
+    elif skip_dev is None:
         call('mmvid_adam_step_rows', *args, _stream())
     else:
         call('mmvid_adam_step_guarded', *args, _p(_chk(skip_dev, torch.int32, 'skip_dev')), _stream())
@@ -561,6 +566,31 @@ def step_guard(sqnorm, grad_scale, step_dev, guard_i, guard_f):
 
 def lr_schedule(step_dev, kind, lr_min, lr_max, warmup, every, lr_out):
     call('mmvid_lr_schedule', _p(step_dev), int(kind), float(lr_min), float(lr_max), int(warmup), int(every), _p(lr_out),
+         _stream())
+
+
+LR_STEP, LR_COSINE, LR_WARMUP_DECAY = 2, 3, 4  # the kinds of mmvid_lr_schedule_ext (0 constant and 1 WarmupLR: mmvid_lr_schedule)
+
+
+def lr_schedule_ext(step_dev, kind, lr_min, lr_max, every, a, b, gamma, lr_out):
+    """lr_out[0] <- the closed-form schedule `kind` at the device step count (include/mmvid_hip_ext.h: mmvid_lr_schedule_ext):
+    2 StepLR(step_size=a, gamma), 3 CosineAnnealingLR(T_max=a, eta_min=lr_min), 4 WarmupDecayLR(total=b, warmup=a)."""
+    _chk(step_dev, f32, 'step_dev'), _chk(lr_out, f32, 'lr_out')
+    if step_dev.numel() < 1 or lr_out.numel() < 1:
+        raise ValueError('lr_schedule_ext: step_dev and lr_out hold one fp32 each')
+    call('mmvid_lr_schedule_ext', _p(step_dev), int(kind), float(lr_min), float(lr_max), int(every), int(a), int(b), float(gamma),
+         _p(lr_out), _stream())
+
+
+def lr_plateau(loss_dev, step_dev, every, factor, patience, cooldown, threshold, min_lr, eps, state_f, state_i, skip_dev=None):
+    """One scheduler step of ReduceLROnPlateau(mode='min', threshold_mode='rel') on the device (include/mmvid_hip_ext.h:
+    mmvid_lr_plateau): state_f (fp32 [2]) = lr, best; state_i (int32 [3]) = bad epochs, cool-down left, reductions.  After the
+    optimiser; it does nothing where skip_dev says the step was skipped or the step count is no multiple of `every`."""
+    _chk(loss_dev, f32, 'loss_dev'), _chk(step_dev, f32, 'step_dev'), _chk(state_f, f32, 'state_f'), _chk(state_i, torch.int32, 'state_i')
+    if loss_dev.numel() != 1 or step_dev.numel() < 1 or state_f.numel() != 2 or state_i.numel() != 3:
+        raise ValueError('lr_plateau: loss_dev and step_dev hold one fp32 each, state_f 2 fp32, state_i 3 int32')
+    call('mmvid_lr_plateau', _p(loss_dev), _p(step_dev), int(every), float(factor), int(patience), int(cooldown), float(threshold),
+         float(min_lr), float(eps), _p(state_f), _p(state_i), None if skip_dev is None else _p(_chk(skip_dev, torch.int32, 'skip_dev')),
          _stream())
 
 
